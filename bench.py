@@ -19,7 +19,14 @@ factors + ZeRO-1, sufficient factors, bucketed all-reduce; parallel/schedule.py)
 time the fastest; the JSON reports every candidate's ms/step and the choice. ``--schedule NAME``
 skips the probes. The job exits non-zero if the replicas' parameters differ after the timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch_size 128] [--schedule auto]
+A plain run does only what the headline needs: set-up, warm-up, the ``--steps`` timed steps, the
+record. ``--full`` adds the measurements that take runs of their own, after the headline: the GPU
+phase breakdown (``"phases_ms"``) and the fp32 step (``"fp32"``). ``--dump-outputs DIR`` writes what
+the last timed step left (parameters, Adam slots, per-row loss / correctness, global step) as
+``DIR/<name>.npy``; the inputs are the same in every run with the same arguments.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch_size 128] [--schedule auto] [--full]
+                    [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -93,8 +100,15 @@ def _args(argv):
                     "the last warm-up step and the timed region (events made and the warm-up loss read beforehand)")
     ap.add_argument("--idle_us", type=float, default=0.0, help="diagnostic: host busy-wait before the timed region "
                     "(GPU idle), to measure what an idle gap costs the first timed steps")
-    ap.add_argument("--phases", type=int, default=1, help="after the timed steps, replay a few steps of a graph "
-                    "with HIP timing events at the phase boundaries and report the GPU phase breakdown (untimed)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run what takes runs of its own: "
+                    "the GPU phase breakdown (--phases) and the fp32 step (--fp32_also). Off: the run sets up, warms "
+                    "up, times --steps steps and prints the record (\"phases_ms\" and \"fp32\" are null)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR", help="after the timed steps, "
+                    "write what the last timed step left (rank 0: fp32 parameters, Adam slots, per-row loss and "
+                    "correctness, global step) as DIR/<name>.npy")
+    ap.add_argument("--phases", type=int, default=1, help="with --full: after the timed steps, replay a few steps of "
+                    "a graph with HIP timing events at the phase boundaries and report the GPU phase breakdown "
+                    "(untimed)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="compute dtype: bf16 MFMA operands "
                     "(fp32 accumulate/master/optimizer), or fp32 everything (the reference's precision)")
     ap.add_argument("--fused_tail", type=int, default=1, help="1: on one GPU the Adam kernel also reduces the "
@@ -106,14 +120,17 @@ def _args(argv):
                     "0: time whatever state the warm-up steps left")
     ap.add_argument("--data", default="strokes", choices=["strokes", "random"], help="device-resident training "
                     "set: learnable class-conditional strokes (default) or uniform noise with random labels")
-    ap.add_argument("--fp32_also", type=int, default=-1, help="after the bf16 headline, time the fp32 step (the "
-                    "reference's precision) with the same protocol and report it under \"fp32\": 1 always, 0 never, "
-                    "-1 at world 1 only")
+    ap.add_argument("--fp32_also", type=int, default=-1, help="with --full: after the bf16 headline, time the fp32 "
+                    "step (the reference's precision) with the same protocol and report it under \"fp32\": 1 always, "
+                    "0 never, -1 at world 1 only")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--cpu", action="store_true", help="plumbing dry-run: fp32 PyTorch CPU runner + Gloo "
                     "(exercises the launcher/barrier/JSON contract without a GPU; not a performance number)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return a
 
 
 def _candidates(a, dp: bool):
@@ -331,7 +348,9 @@ def main(argv=None):
     res = _measure(a, ctx, data, labels, sched, wd, "bf16" if a.dtype == "bf16" else "fp32")
     job, tr, eng = res["job"], res["job"].tr, res["job"].eng
     topo = _job_topology(ctx, dev, tr, eng)
-    phases = _phase_breakdown(eng, job.stream, job.graph_mode, world, ctx) if a.phases else None
+    if a.dump_outputs and rank == 0:  # before anything below runs further steps on this engine
+        _dump_outputs(a.dump_outputs, _step_outputs(eng))
+    phases = _phase_breakdown(eng, job.stream, job.graph_mode, world, ctx) if a.full and a.phases else None
     # the phase steps ran on the job's stream: wait for them before reading the state on the default
     # stream (without this the last step's loss rows could be read mid-write: two runs of the same
     # binary printed the loss of step N or N - 1)
@@ -347,7 +366,7 @@ def main(argv=None):
     # timed in the same process after the bf16 headline: same steps, warm-up and learning-state
     # protocol, reported beside it. World 1 by default (--fp32_also -1).
     fp32 = None
-    if a.dtype == "bf16" and (a.fp32_also == 1 or (a.fp32_also < 0 and world == 1)):
+    if a.full and a.dtype == "bf16" and (a.fp32_also == 1 or (a.fp32_also < 0 and world == 1)):
         job.eng = None
         del res, job, eng
         torch.cuda.synchronize(dev)
@@ -569,6 +588,31 @@ def _state_tensors(eng):
     return [eng.params(), eng.params_bf16(), eng.adam_m(), eng.adam_v(), eng.step_tensor()]
 
 
+def _step_outputs(eng):
+    """What a caller of the training step holds after its last step, as host arrays: the updated
+    fp32 master parameters and Adam slots (flat, the engine's layout), the step's per-row loss and
+    correctness, and the global step. 3 x 13.1 MB + 2 x B floats: everything, no sampling. The
+    inputs are the same in every run with the same arguments (seeded data set, permutation, init and
+    dropout key; the timed steps start from the restored --state_steps snapshot), so two builds can
+    be compared array by array."""
+    import numpy as np
+
+    def host(t):
+        return t.detach().float().cpu().numpy().astype(np.float32, copy=False)
+
+    return {"params": host(eng.params()), "adam_m": host(eng.adam_m()), "adam_v": host(eng.adam_v()),
+            "loss_rows": host(eng.loss_rows()), "correct_rows": host(eng.correct_rows()),
+            "global_step": np.asarray([int(eng.step_tensor().item())], dtype=np.float64)}
+
+
+def _dump_outputs(path, outs):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def _job_topology(ctx, dev, tr, eng):
     """What the job really ran on, for the JSON: the communicator's own world size, every rank's
     device (index + PCI bus / uuid), and whether the replicas' parameters are bit-identical after
@@ -692,6 +736,8 @@ def _cpu_dry_run(a):
     dt = ctx.max_scalar(time.perf_counter() - t0)
     digest = float(st.runner.params().double().sum())
     hi, lo = ctx.max_scalar(digest), -ctx.max_scalar(-digest)
+    if a.dump_outputs and rank == 0:
+        _dump_outputs(a.dump_outputs, {"params": st.runner.params().detach().float().cpu().numpy()})
     if rank == 0:
         print(json.dumps({"metric": "images/sec (whole node) MNIST CNN DP [CPU dry-run]", "value": world * a.batch_size * a.steps / dt,
                           "unit": "images/s", "n_gpus": 0, "n_ranks": world, "steps": a.steps, "warmup": a.warmup,

@@ -296,7 +296,7 @@ def _bench(args, nproc=1, timeout=300, script="bench.py", self_launch=False):
 @pytest.mark.parametrize("sfb,zero", [(1, 0), (0, 0), (1, 1)])
 def test_bench_two_ranks_one_gpu_over_ipc(cuda, sfb, zero):
     r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--min_warmup_ms", "50", "--fc_sfb", str(sfb),
-                "--zero", str(zero)], nproc=2)
+                "--zero", str(zero), "--full"], nproc=2)  # --full: the phase breakdown asserted below
     assert r["config"]["zero1_fc1"] == bool(zero)
     kind = "ipc+sfb" if sfb else "ipc"
     assert r["n_gpus"] == 2 and r["config"]["dp_transport"] == kind and r["config"]["parallelism"] == "dp2"
@@ -354,6 +354,30 @@ def test_bench_four_ranks_zero(cuda):
     assert r["config"]["zero1_fc1"] and r["config"]["dp_transport"] == "ipc+sfb" and r["n_gpus"] == 4
     assert r["value"] > 0 and r["config"]["global_batch"] == 512
     assert r["comm_world"] == 4 and r["replicas_identical"], r
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(cuda, tmp_path):
+    """A plain ``bench.py --gpus 1`` run times exactly ``--steps`` steps from the ``--state_steps``
+    snapshot and runs nothing after them (no phase breakdown, no fp32 step: both null, and the
+    global step is state_steps + steps); ``--dump-outputs`` leaves what the last timed step left as
+    finite float32 / float64 arrays of at most 64 MB."""
+    import numpy as np
+
+    r = _bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--min_warmup_ms", "50", "--dump-outputs",
+                str(tmp_path)])
+    assert r["steps"] == 7 and r["ms_per_step"] > 0 and r["value"] > 0 and r["dtype"] == "bf16"
+    assert abs(r["value"] - 128 * 1e3 / r["ms_per_step"]) <= 1e-3 * r["value"]
+    assert r["phases_ms"] is None and r["fp32"] is None
+    assert r["train_state"]["global_step"] == 100 + 7
+    out = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert set(out) == {"params", "adam_m", "adam_v", "loss_rows", "correct_rows", "global_step"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64e6
+    assert out["params"].dtype == np.float32 and out["params"].shape == out["adam_m"].shape == out["adam_v"].shape
+    assert out["loss_rows"].shape == out["correct_rows"].shape == (128,)
+    assert int(out["global_step"][0]) == 107 and out["adam_v"].min() >= 0 and out["adam_m"].any()
+    assert abs(float(out["loss_rows"].mean()) - r["train_state"]["loss_after_timed"]) <= 1e-3 * abs(
+        r["train_state"]["loss_after_timed"]) + 1e-4
 
 
 def test_bench_fp32_dtype(cuda):

@@ -51,6 +51,30 @@ def test_bench_refuses_wrong_world():
     assert "WORLD_SIZE=1" in p.stderr and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_cpu_dump_outputs_and_step_count(tmp_path):
+    """``--dump-outputs DIR`` of the CPU dry run: the parameters after the last timed step as
+    float32 ``DIR/params.npy``, the same bytes in a second run with the same arguments; the record
+    carries ``ms_per_step`` and the ``--steps`` it was asked for; ``--steps 0`` is refused."""
+    import numpy as np
+
+    recs, arrs = [], []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--steps", "3", "--warmup", "1",
+                            "--batch_size", "8", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True,
+                           timeout=120, env=_clean_env(), cwd=ROOT)
+        assert p.returncode == 0, p.stdout + p.stderr
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        recs.append(json.loads(lines[0]))
+        arrs.append(np.load(tmp_path / d / "params.npy"))
+    assert recs[0]["steps"] == 3 and recs[0]["ms_per_step"] > 0
+    assert arrs[0].dtype == np.float32 and arrs[0].size > 3_000_000 and np.isfinite(arrs[0]).all()
+    assert np.array_equal(arrs[0], arrs[1])
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--steps", "0"], capture_output=True,
+                       text=True, timeout=120, env=_clean_env(), cwd=ROOT)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def test_spawn_fails_fast_when_a_rank_fails(tmp_path):
     script = tmp_path / "job.py"
     script.write_text(textwrap.dedent("""
