@@ -17,25 +17,48 @@ int64_t crc32c_op(const at::Tensor& bytes, int64_t init) {
   return (int64_t)crc32c_extend((uint32_t)init, bytes.data_ptr(), (size_t)bytes.nbytes());
 }
 
+// the optional trailing schedule arguments of the flat ops: no lr_params = constant at `lr`
+LrSchedule flat_schedule(double lr, const std::string& kind, const std::vector<double>& params,
+                         const std::vector<int64_t>& boundaries, const std::vector<double>& values) {
+  if (kind == "constant" && params.empty()) return lr_constant((float)lr);
+  // lr_params[0] is the base rate: the positional lr must say the same, not be silently ignored
+  TORCH_CHECK(params.empty() || (float)params[0] == (float)lr, "lr (", lr, ") and lr_params[0] (", params[0], ") disagree");
+  try {
+    return make_lr_schedule(kind, params.empty() ? std::vector<double>{lr} : params, boundaries, values);
+  } catch (const std::invalid_argument& e) {
+    TORCH_CHECK(false, e.what());
+  }
+}
+
+// Adam's t = *step + t_offset; the schedule is evaluated on the device at s = t - 1
 void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf, double lr,
-               double b1, double b2, double eps, at::Tensor step, double grad_scale) {
+               double b1, double b2, double eps, at::Tensor step, double grad_scale, int64_t t_offset,
+               std::string lr_kind, std::vector<double> lr_params, std::vector<int64_t> lr_boundaries,
+               std::vector<double> lr_values) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "adam_flat: fp32 GPU params");
   TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel() && g.numel() == p.numel(), "adam_flat: sizes");
   TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam_flat: int64 GPU step");
   const bool gb = g.scalar_type() == at::kBFloat16;
   AdamArgs a{(float*)p.data_ptr(), (float*)m.data_ptr(), (float*)v.data_ptr(), gb ? nullptr : (const float*)g.data_ptr(),
              pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-             (float)lr, (float)b1, (float)b2, (float)eps, (const int64_t*)step.data_ptr(), 1, (float)grad_scale};
+             flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
+             (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
   adam_apply(a, cur());
 }
 
 void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
-                   double lr, double momentum, double weight_decay, bool nesterov, double grad_scale) {
+                   double lr, double momentum, double weight_decay, bool nesterov, double grad_scale,
+                   c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind, std::vector<double> lr_params,
+                   std::vector<int64_t> lr_boundaries, std::vector<double> lr_values) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "momentum_flat: fp32 GPU params");
+  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), "momentum_flat: int64 GPU step");
+  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
+  TORCH_CHECK(sc.kind == LR_CONSTANT || step, "momentum_flat: a schedule needs the device step tensor");
   const bool gb = g.scalar_type() == at::kBFloat16;
   SgdArgs a{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
             pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-            (float)lr, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0};
+            sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
+            step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
   sgd_apply(a, cur());
 }
 
@@ -50,6 +73,17 @@ void roofline_stream(at::Tensor p, at::Tensor m, at::Tensor v, const at::Tensor&
   stream_floor((float*)p.data_ptr(), (float*)m.data_ptr(), (float*)v.data_ptr(), (const uint16_t*)g.data_ptr(),
                (uint16_t*)pbf.data_ptr(), x ? (const float*)x->data_ptr() : nullptr, n / 4, nx / 4, (int)blocks,
                (int)unroll, cur());
+}
+
+// the device lr_at() over a vector of steps (the numerical probe of the schedule tests)
+at::Tensor lr_schedule_eval_op(const at::Tensor& steps, std::string kind, std::vector<double> params,
+                               std::vector<int64_t> boundaries, std::vector<double> values) {
+  TORCH_CHECK(steps.is_cuda() && steps.scalar_type() == at::kLong && steps.dim() == 1, "lr_schedule_eval: [n] int64 GPU steps");
+  const LrSchedule sc = flat_schedule(params.empty() ? 0.0 : params[0], kind, params, boundaries, values);
+  auto sc_steps = steps.contiguous();
+  auto out = at::empty({sc_steps.numel()}, sc_steps.options().dtype(at::kFloat));
+  lr_schedule_eval(sc, (const int64_t*)sc_steps.data_ptr(), (float*)out.data_ptr(), sc_steps.numel(), cur());
+  return out;
 }
 
 void noop_op(int64_t blocks) { noop_launch((int)blocks, cur()); }
@@ -67,14 +101,18 @@ TORCH_LIBRARY(tfd, m) {
   m.def("crc32c(Tensor bytes, int init=0) -> int");
   m.impl("crc32c", c10::DispatchKey::CPU, &crc32c_op);
   m.def("adam_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, float lr, float b1, float b2, "
-        "float eps, Tensor(e!) step, float grad_scale=1.0) -> ()");
+        "float eps, Tensor(e!) step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
+        "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[]) -> ()");
   m.impl("adam_flat", c10::DispatchKey::CUDA, &adam_flat);
   m.def("momentum_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
-        "float weight_decay, bool nesterov, float grad_scale=1.0) -> ()");
+        "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
+        "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[]) -> ()");
   m.impl("momentum_flat", c10::DispatchKey::CUDA, &momentum_flat);
   m.def("roofline_stream(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!) pbf, Tensor? x, int blocks, "
         "int unroll) -> ()");
   m.impl("roofline_stream", c10::DispatchKey::CUDA, &roofline_stream);
+  m.def("lr_schedule_eval(Tensor steps, str kind, float[] params, int[] boundaries=[], float[] values=[]) -> Tensor");
+  m.impl("lr_schedule_eval", c10::DispatchKey::CUDA, &lr_schedule_eval_op);
   m.def("noop(int blocks) -> ()");
   m.impl("noop", c10::DispatchKey::CompositeExplicitAutograd, &noop_op);
   m.def("to_bf16(Tensor x) -> Tensor");

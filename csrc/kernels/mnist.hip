@@ -25,6 +25,7 @@
 #include "../gemm256.h"  // kc_slot, make_rsrc, DenseSrc (the fc1 dX DMA ring)
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
+#include "../mnist_tail.h"
 
 #include <algorithm>
 #include <stdexcept>
@@ -34,9 +35,6 @@
 constexpr int GEMM_RS = 2;       // register stages of the LDS-staged GEMM core (csrc/gemm.h)
 constexpr int FDX_BK_ = 128;     // fc1 dX K-tile
 constexpr int FDW_BK_ = 64;      // fc1 dW K-tile
-// fc-region Adam: strides per lane with all loads issued up front (1: -0.5 us/step against 2 with the
-// round-6 kernels, 4: +0.6; profiles/mnist_conv2_wgrad_grouping_r6.log)
-constexpr int ADAM_U = 1;
 constexpr int FC1_BK_ = 32;      // one-shot fc1: 14 K-tiles of 32 (140 KiB LDS), 0.6 us/step faster than 7 of 64
 
 namespace tfd {
@@ -81,20 +79,6 @@ __device__ __forceinline__ int data_row_use(const MnistStepArgs& a, const RowPre
   if (a.rows && r.tag == (int)r.step) return r.row;
   return a.perm[(int)((r.step * (int64_t)a.B + b) % (int64_t)a.n_data)];
 }
-// gather block b: the batch row b of step `next` into rows / xpre / ypre; block 0 also writes the
-// tag (visibility to the next kernel is the kernel boundary)
-__device__ __forceinline__ void gather_next(const MnistStepArgs& a, int64_t next, int b) {
-  const int row = a.perm[(int)((next * (int64_t)a.B + b) % (int64_t)a.n_data)];
-  const f32x4* src = reinterpret_cast<const f32x4*>(a.data + (size_t)row * 784);
-  f32x4* dst = reinterpret_cast<f32x4*>(a.xpre + (size_t)b * 784);
-  for (int i = threadIdx.x; i < 196; i += blockDim.x) dst[i] = src[i];
-  if (threadIdx.x == 0) {
-    a.rows[b] = row;
-    a.ypre[b] = a.labels[row];
-    if (b == 0) a.rows[a.B] = (int)next;
-  }
-}
-__device__ __forceinline__ int gather_blocks(const MnistStepArgs& a) { return (a.perm && a.xpre) ? a.B : 0; }
 // the prefetched label of batch row b (speculative load beside the tag and the step)
 __device__ __forceinline__ int batch_label(const MnistStepArgs& a, int b) {
   if (a.perm && a.xpre) {
@@ -1435,162 +1419,6 @@ __global__ __launch_bounds__(256) void fc_grad_sfb(MnistStepArgs a, int gb, int 
   fc1_dw_tile(a, la, lb, (id / FDW_GX) * FDW_BM, (id % FDW_GX) * FDW_BN, WB, (bf16*)smem_raw);
 }
 
-// ---------------- one-GPU optimizer tail: K16 ApplyAdam with the K12/K14/K15 slab reduce fused ----------------
-// Grid = [13 conv1 blocks | 201 conv2 blocks | MAD_FC_BLOCKS grid-stride blocks]:
-//   conv1: block owns 16 float4 of the 832 conv1 weight/bias gradients; thread (q = t >> 4, x = t & 15)
-//          sums slabs q, q + 16, ... of float4 x (16-lane groups read 256 contiguous bytes per slab,
-//          every load issued before the first add), then the 16 partials are summed in LDS in q order;
-//   conv2: block owns 64 float4; thread (q = t >> 6, x = t & 63) sums slabs q, q + 4, ... (each wave
-//          reads 1 KiB contiguous per slab), then 4 partials in LDS in q order;
-//   fc:    plain grid-stride Adam over the flat gradient buffer.
-// Every gradient reduction is deterministic (fixed order). t comes from the head kernel
-// (MnistStepArgs::t_out), so nothing here reads the global_step that the last block bumps.
-// (The previous layout -- one 16-lane group per float4, each lane a different slab -- made every
-//  wave instruction touch 64 scattered 16-B pieces: 7.6 us for the conv region alone.)
-constexpr int MAD_NT = 256;
-constexpr int MAD_C1F4 = (int)(OFF_WC2 / 4);   // 208
-constexpr int MAD_C2END = (int)(OFF_WD1 / 4);  // 13024
-constexpr int MAD_C1BLK = MAD_C1F4 / 16;       // 13
-constexpr int MAD_C2BLK = (MAD_C2END - MAD_C1F4 + 63) / 64;  // 201
-constexpr int MAD_FC_BLOCKS = 1024;  // grid-stride blocks of the fc-region Adam (512 / 2048: within noise)
-constexpr int MAD_CONV = MAD_C1BLK + MAD_C2BLK;
-static_assert(MAD_C1F4 % 16 == 0, "conv1 region: whole blocks");
-constexpr int MAD_SL = 16;  // slab loads in flight per thread
-__device__ __forceinline__ void adam4_pre(const MnistAdamArgs& o, int64_t i, f32x4 p, f32x4 m, f32x4 v, f32x4 g,
-                                          float lr_t, float c1, float c2) {
-  m = m + (g - m) * c1;
-  v = v + (g * g - v) * c2;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] -= lr_t * m[j] / (sqrtf(v[j]) + o.eps);
-  reinterpret_cast<f32x4*>(o.p)[i] = p;
-  reinterpret_cast<f32x4*>(o.m)[i] = m;
-  reinterpret_cast<f32x4*>(o.v)[i] = v;
-  if (o.pbf) reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
-}
-__device__ __forceinline__ void adam4(const MnistAdamArgs& o, int64_t i, f32x4 g, float lr_t, float c1, float c2) {
-  f32x4 p = reinterpret_cast<f32x4*>(o.p)[i];
-  f32x4 m = reinterpret_cast<f32x4*>(o.m)[i];
-  f32x4 v = reinterpret_cast<f32x4*>(o.v)[i];
-  m = m + (g - m) * c1;
-  v = v + (g * g - v) * c2;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] -= lr_t * m[j] / (sqrtf(v[j]) + o.eps);
-  reinterpret_cast<f32x4*>(o.p)[i] = p;
-  reinterpret_cast<f32x4*>(o.m)[i] = m;
-  reinterpret_cast<f32x4*>(o.v)[i] = v;
-  if (o.pbf) reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
-}
-// sum over slabs q, q + QS, ... (< ns) of float4 column x of a [ns][stride4] slab array; MAD_SL loads
-// issued per batch before any add
-template <int QS>
-__device__ __forceinline__ f32x4 slab_sum(const f32x4* __restrict__ s4, int64_t stride4, int ns, int q, int x) {
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = q; k0 < ns; k0 += QS * MAD_SL) {
-    f32x4 v[MAD_SL];
-#pragma unroll
-    for (int u = 0; u < MAD_SL; ++u) {
-      const int k = k0 + u * QS;
-      v[u] = k < ns ? s4[(size_t)k * stride4 + x] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < MAD_SL; ++u) acc += v[u];
-  }
-  return acc;
-}
-__global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel(MnistStepArgs a, MnistAdamArgs o, int fcb4) {
-  const int gb = gather_blocks(a);
-  if ((int)blockIdx.x < gb) {  // the next step's batch; t = the step started next
-    gather_next(a, *o.t, blockIdx.x);
-    return;
-  }
-  const int grid = (int)gridDim.x - gb;
-  // grid == MAD_CONV: the conv region only; the last conv2 block bumps the step
-  if (grid == MAD_CONV && (int)blockIdx.x - gb == grid - 1 && threadIdx.x == 0) *o.step += 1;
-  // t (a dependent load of the head's step counter) is awaited only where the update needs it,
-  // after this thread's first operand loads are out (the optimizer's first memory round trip)
-  auto lr_of = [&]() {
-    const int64_t t = *o.t;
-    const float b1p = powf(o.beta1, (float)t), b2p = powf(o.beta2, (float)t);
-    return o.lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  };
-  const float c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
-  const int bid = (int)blockIdx.x - gb, tid = threadIdx.x;
-  if (bid < MAD_CONV) {
-    __shared__ f32x4 red[MAD_NT];
-    const bool one = bid < MAD_C1BLK;
-    const int q = one ? tid >> 4 : tid >> 6, x = one ? tid & 15 : tid & 63;
-    const int64_t i = one ? (int64_t)bid * 16 + x : MAD_C1F4 + (int64_t)(bid - MAD_C1BLK) * 64 + x;
-    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (one) {
-      g = slab_sum<16>(reinterpret_cast<const f32x4*>(a.wg1_slab) + i, 832 / 4, 2 * a.B, q, 0);
-    } else if (i < MAD_C2END) {
-      g = slab_sum<4>(reinterpret_cast<const f32x4*>(a.wg2_slab) + (i - MAD_C1F4), 801 * 64 / 4, a.wg2_splits, q, 0);
-    }
-    red[tid] = g;
-    __syncthreads();
-    if (q == 0 && i < MAD_C2END) {
-      const int nq = one ? 16 : 4, qs = one ? 16 : 64;
-      f32x4 s = red[x];
-      for (int k = 1; k < nq; ++k) s += red[k * qs + x];
-      adam4(o, i, s, lr_of(), c1, c2);
-    }
-  } else {
-    const int64_t i0 = fcb4 + (int64_t)(bid - MAD_CONV) * MAD_NT + tid;  // fcb4: MAD_C2END, or the out layer
-    const int64_t STRIDE = (int64_t)(grid - MAD_CONV) * MAD_NT;
-    // ADAM_U strides' loads issued before any math/store, so U x 56 B per lane are in flight
-    // (the one-at-a-time loop leaves the compiler no room: p/m/v stores may alias the next loads;
-    // streaming non-temporal loads/stores were +0.9 us: the next step re-reads p/m/v from MALL)
-    if (o.gbf) {
-      constexpr int U = ADAM_U;
-      const float lr_t = lr_of();
-      for (int64_t base = i0; base < TOTAL / 4; base += STRIDE * U) {
-        uint2 h[U];
-        f32x4 p[U], m[U], v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int64_t i = base + (int64_t)u * STRIDE;
-          if (i < TOTAL / 4) {
-            p[u] = reinterpret_cast<const f32x4*>(o.p)[i];
-            h[u] = reinterpret_cast<const uint2*>(o.gbf)[i];
-            m[u] = reinterpret_cast<const f32x4*>(o.m)[i];
-            v[u] = reinterpret_cast<const f32x4*>(o.v)[i];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int64_t i = base + (int64_t)u * STRIDE;
-          if (i < TOTAL / 4) {
-            const f32x4 g = f32x4{__uint_as_float(h[u].x << 16), __uint_as_float(h[u].x & 0xFFFF0000u),
-                                  __uint_as_float(h[u].y << 16), __uint_as_float(h[u].y & 0xFFFF0000u)};
-            m[u] = m[u] + (g - m[u]) * c1;
-            v[u] = v[u] + (g * g - v[u]) * c2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[u][j] -= lr_t * m[u][j] / (sqrtf(v[u][j]) + o.eps);
-            reinterpret_cast<f32x4*>(o.p)[i] = p[u];
-            reinterpret_cast<f32x4*>(o.m)[i] = m[u];
-            reinterpret_cast<f32x4*>(o.v)[i] = v[u];
-            reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[u][0], p[u][1]), pack_bf2(p[u][2], p[u][3]));
-          }
-        }
-      }
-    } else {
-      // the first item's p / m / v / g are loaded before t is awaited
-      f32x4 p0 = {}, m0 = {}, v0 = {}, g0 = {};
-      if (i0 < TOTAL / 4) {
-        p0 = reinterpret_cast<const f32x4*>(o.p)[i0];
-        m0 = reinterpret_cast<const f32x4*>(o.m)[i0];
-        v0 = reinterpret_cast<const f32x4*>(o.v)[i0];
-        g0 = reinterpret_cast<const f32x4*>(a.grad)[i0];
-      }
-      const float lr_t = lr_of();
-      if (i0 < TOTAL / 4) adam4_pre(o, i0, p0, m0, v0, g0, lr_t, c1, c2);
-      for (int64_t i = i0 + STRIDE; i < TOTAL / 4; i += STRIDE)
-        adam4(o, i, reinterpret_cast<const f32x4*>(a.grad)[i], lr_t, c1, c2);
-    }
-    if (bid == grid - 1 && tid == 0) *o.step += 1;  // see MnistAdamArgs
-  }
-}
-
 template <auto K>
 inline void set_smem(int bytes) {  // raise the kernel's dynamic-LDS limit to the largest size asked so far
   static int limit = 64 * 1024;
@@ -1663,8 +1491,10 @@ void mnist_conv_grad_reduce(const MnistStepArgs& a, hipStream_t s) {
 }
 
 void mnist_adam_fused(const MnistStepArgs& a, const MnistAdamArgs& o, hipStream_t s, bool fc_region) {
-  const int gb = (a.perm && a.xpre) ? a.B : 0;
-  mnist_adam_kernel<<<gb + MAD_CONV + (fc_region ? MAD_FC_BLOCKS : 0), MAD_NT, 0, s>>>(a, o, (int)(OFF_WD1 / 4));
+  // a constant rate launches this file's instantiation (the tail as it was before schedules); one that
+  // carries a schedule lives in its own code object (mnist_tail_sched.hip)
+  if (o.sched.kind == LR_CONSTANT) mnist_adam_launch(a, mnist_adam_const(o), s, fc_region);
+  else mnist_adam_fused_sched(a, o, s, fc_region);
 }
 
 int64_t mnist_sfb_slot_elems(int B) { return ((int64_t)B * (2 * HID + 2 * NCLS) + 63) / 64 * 64; }

@@ -12,124 +12,10 @@
 #include <stdexcept>
 #include "../common.h"
 #include "../tfd_kernels.h"
+#include "../optim_kernels.h"
 
 namespace tfd {
 namespace {
-
-constexpr int kOptThreads = 256;
-constexpr int kOptMaxBlocks = 2048;
-
-struct AdamItem {
-  f32x4 p, m, v, g;
-};
-__device__ __forceinline__ AdamItem adam_load4(const AdamArgs& a, int64_t i) {
-  AdamItem x;
-  x.p = reinterpret_cast<const f32x4*>(a.p)[i];
-  x.m = reinterpret_cast<const f32x4*>(a.m)[i];
-  x.v = reinterpret_cast<const f32x4*>(a.v)[i];
-  if (a.gbf) {
-    const uint2 gb = reinterpret_cast<const uint2*>(a.gbf)[i];
-    x.g = f32x4{bf2f((uint16_t)(gb.x & 0xFFFF)), bf2f((uint16_t)(gb.x >> 16)), bf2f((uint16_t)(gb.y & 0xFFFF)),
-                bf2f((uint16_t)(gb.y >> 16))};
-  } else {
-    x.g = reinterpret_cast<const f32x4*>(a.g)[i];
-  }
-  return x;
-}
-__device__ __forceinline__ void adam_apply4(const AdamArgs& a, int64_t i, AdamItem x, float lr_t, float c1, float c2) {
-  const f32x4 g = x.g * a.grad_scale;
-  f32x4 p = x.p, m = x.m, v = x.v;
-  m = m + (g - m) * c1;
-  v = v + (g * g - v) * c2;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] -= lr_t * m[j] / (sqrtf(v[j]) + a.eps);
-  reinterpret_cast<f32x4*>(a.p)[i] = p;
-  reinterpret_cast<f32x4*>(a.m)[i] = m;
-  reinterpret_cast<f32x4*>(a.v)[i] = v;
-  if (a.pbf) reinterpret_cast<uint2*>(a.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
-}
-__global__ __launch_bounds__(kOptThreads) void adam_kernel(AdamArgs a) {
-  // the first item's operands are loaded before t (a dependent load of the step counter) is awaited
-  const int64_t n4 = a.n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * kOptThreads;
-  const int64_t i0 = (int64_t)blockIdx.x * kOptThreads + threadIdx.x;
-  AdamItem x{};
-  if (i0 < n4) x = adam_load4(a, i0);
-  const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
-  const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
-  const float lr_t = a.lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
-  for (int64_t i = i0; i < n4; i += stride) {
-    if (i != i0) x = adam_load4(a, i);
-    adam_apply4(a, i, x, lr_t, c1, c2);
-  }
-  // scalar tail (n % 4)
-  for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
-    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale;
-    float m = a.m[i] + (g - a.m[i]) * c1;
-    float v = a.v[i] + (g * g - a.v[i]) * c2;
-    const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
-    a.p[i] = p; a.m[i] = m; a.v[i] = v;
-    if (a.pbf) a.pbf[i] = f2bf_bits(p);
-  }
-}
-
-struct AdamRanges {
-  int nr;
-  int64_t beg4[3], pre4[4];  // range starts and prefix sums in float4 units
-  int64_t tail_beg, tail_n;  // the last range's n % 4 scalar elements
-};
-// same per-element math as adam_kernel, over a table of ranges (the logical float4 index is mapped
-// to its range by the prefix sums)
-__global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(AdamArgs a, AdamRanges r) {
-  // the first item's operands are loaded before t (a dependent load of the step counter) is awaited:
-  // for the small conv + output-layer launch of the DP step that is one memory round trip of its ~3
-  const int64_t stride = (int64_t)gridDim.x * kOptThreads;
-  auto phys = [&](int64_t i) {
-    const int k = i < r.pre4[1] ? 0 : (r.nr > 2 && i >= r.pre4[2] ? 2 : 1);
-    return r.beg4[k] + (i - r.pre4[k]);
-  };
-  int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x;
-  AdamItem x{};
-  if (i < r.pre4[r.nr]) x = adam_load4(a, phys(i));
-  const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
-  const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
-  const float lr_t = a.lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
-  for (; i < r.pre4[r.nr]; i += stride) {
-    const int64_t pi = phys(i);
-    if (i != (int64_t)blockIdx.x * kOptThreads + threadIdx.x) x = adam_load4(a, pi);
-    adam_apply4(a, pi, x, lr_t, c1, c2);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < r.tail_n) {
-    const int64_t i = r.tail_beg + threadIdx.x;
-    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale;
-    const float m = a.m[i] + (g - a.m[i]) * c1;
-    const float v = a.v[i] + (g * g - a.v[i]) * c2;
-    const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
-    a.p[i] = p; a.m[i] = m; a.v[i] = v;
-    if (a.pbf) a.pbf[i] = f2bf_bits(p);
-  }
-}
-
-// GradientDescent / Momentum (TF ApplyMomentum: accum = accum*mu + g; p -= lr*accum,
-// nesterov: p -= lr*(g + mu*accum)); optional decoupled-from-nothing L2 weight decay folded in g.
-__global__ __launch_bounds__(kOptThreads) void sgd_kernel(SgdArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * kOptThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
-    float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale + a.weight_decay * a.p[i];
-    float p = a.p[i];
-    if (a.mom) {
-      const float acc = a.mom[i] * a.momentum + g;
-      a.mom[i] = acc;
-      p -= a.nesterov ? a.lr * (g + a.momentum * acc) : a.lr * acc;
-    } else {
-      p -= a.lr * g;
-    }
-    a.p[i] = p;
-    if (a.pbf) a.pbf[i] = f2bf_bits(p);
-  }
-}
 
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -201,15 +87,13 @@ __global__ __launch_bounds__(kOptThreads) void stream_floor_kernel(float* __rest
 // an empty kernel: the dependent-launch boundary floor of a chain of launches
 __global__ void noop_kernel() {}
 
-inline int blocks_for(int64_t n, int per_thread) {
-  const int64_t b = (n / per_thread + kOptThreads - 1) / kOptThreads;
-  return (int)(b < 1 ? 1 : (b > kOptMaxBlocks ? kOptMaxBlocks : b));
-}
-
 }  // namespace
 
 void adam_apply(const AdamArgs& a, hipStream_t s) {
-  adam_kernel<<<blocks_for(a.n, 4), kOptThreads, 0, s>>>(a);
+  // a constant rate launches this file's instantiations (the kernels as they were before schedules);
+  // the ones that carry a schedule live in their own code object (optim_sched.hip)
+  if (a.sched.kind == LR_CONSTANT) adam_kernel<<<blocks_for(a.n, 4), kOptThreads, 0, s>>>(adam_const(a));
+  else adam_apply_sched(a, s);
 }
 void adam_apply_ranges(const AdamArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s) {
   if (nr < 1 || nr > 3) throw std::runtime_error("adam_apply_ranges: 1..3 ranges");
@@ -223,7 +107,9 @@ void adam_apply_ranges(const AdamArgs& a, int nr, const int64_t* beg, const int6
   }
   r.tail_beg = beg[nr - 1] + n[nr - 1] / 4 * 4;
   r.tail_n = n[nr - 1] % 4;
-  adam_ranges_kernel<<<blocks_for(r.pre4[nr] * 4, 4), kOptThreads, 0, s>>>(a, r);
+  const int nb = blocks_for(r.pre4[nr] * 4, 4);
+  if (a.sched.kind == LR_CONSTANT) adam_ranges_kernel<<<nb, kOptThreads, 0, s>>>(adam_const(a), r);
+  else adam_ranges_sched(a, r, nb, s);
 }
 void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf, const float* x, int64_t n4, int64_t nx4,
                   int blocks, int unroll, hipStream_t s) {
@@ -235,7 +121,8 @@ void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf
 }
 void noop_launch(int blocks, hipStream_t s) { noop_kernel<<<blocks < 1 ? 1 : blocks, 64, 0, s>>>(); }
 void sgd_apply(const SgdArgs& a, hipStream_t s) {
-  sgd_kernel<<<blocks_for(a.n, 1), kOptThreads, 0, s>>>(a);
+  if (a.sched.kind == LR_CONSTANT) sgd_kernel<<<blocks_for(a.n, 1), kOptThreads, 0, s>>>(sgd_const(a));
+  else sgd_apply_sched(a, s);
 }
 void cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s) {
   cast_f32_bf16_kernel<<<blocks_for(n, 1), kOptThreads, 0, s>>>(x, y, n);

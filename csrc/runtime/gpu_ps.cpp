@@ -105,8 +105,8 @@ class GpuPsShard : public torch::CustomClassHolder {
   // opt: 0 Adam (lr, b1, b2, eps), 1 GradientDescent (lr), 2 Momentum (lr, momentum), 3 Nesterov
   GpuPsShard(int64_t device, at::Tensor ranges, int64_t flat_total, int64_t n_workers, int64_t opt, double lr,
              double b1, double b2, double eps, double momentum, bool sync)
-      : device_(device), total_(flat_total), nw_(n_workers), opt_(opt), lr_(lr), b1_(b1), b2_(b2), eps_(eps),
-        mom_(momentum), sync_(sync) {
+      : device_(device), total_(flat_total), nw_(n_workers), opt_(opt), b1_(b1), b2_(b2), eps_(eps),
+        mom_(momentum), sync_(sync), sched_(lr_constant((float)lr)) {
     n_ = read_ranges(ranges, &ranges_);
     for (auto& r : ranges_) TORCH_CHECK(r.first + r.second <= flat_total, "range past the flat buffer");
     TORCH_CHECK(n_workers >= 1 && n_workers <= 1024, "n_workers");
@@ -134,12 +134,30 @@ class GpuPsShard : public torch::CustomClassHolder {
 
   int64_t numel() const { return n_; }
   int64_t updates() const { return t_; }
+  // learning-rate schedule over this shard's update count (csrc/lr_schedule.h; the engine's
+  // set_lr_schedule): evaluated on the host per update with s = updates()
+  void set_lr_schedule(std::string kind, std::vector<double> params, std::vector<int64_t> boundaries,
+                       std::vector<double> values) {
+    try {
+      sched_ = make_lr_schedule(kind, params, boundaries, values);
+    } catch (const std::invalid_argument& e) {
+      TORCH_CHECK(false, e.what());
+    }
+  }
+  double current_lr() const { return (double)lr_at(sched_, t_); }
   // 1 (default): peer-buffer copies by a copy kernel on the shard's stream; 0: hipMemcpyAsync
   void set_copy_kernel(bool on) { copy_kernel_ = on; }
   at::Tensor params() { return params_.narrow(0, 0, n_); }
   at::Tensor slot_m() { return m_.narrow(0, 0, n_); }
   at::Tensor slot_v() { return v_.narrow(0, 0, n_); }
   at::Tensor mailbox() { return export_ptr(mail_, nw_ * slot_ * (int64_t)sizeof(float)); }
+  // TEST ONLY: worker w's mailbox slot as a tensor of this process, for in-process tests of one shard
+  // (a same-process writer cannot open its own IPC export). The service never calls it: workers
+  // reach the mailbox through GpuPsPort::push_grad.
+  at::Tensor test_mailbox_slot(int64_t w) {
+    TORCH_CHECK(w >= 0 && w < nw_, "worker index");
+    return at::from_blob(mail_ + w * slot_, {n_}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device_));
+  }
   void open_worker(int64_t w, at::Tensor exported) {
     TORCH_CHECK(w >= 0 && w < nw_, "worker index");
     workers_[w].open(exported);
@@ -193,13 +211,14 @@ class GpuPsShard : public torch::CustomClassHolder {
  private:
   void step_with(const float* g, double scale) {
     if (n_ == 0) { ++t_; return; }
+    const LrSchedule lr = lr_constant(lr_at(sched_, t_));  // s = the update count before this update
     if (opt_ == 0) {
       AdamArgs a{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(), g, nullptr, nullptr, n_,
-                 (float)lr_, (float)b1_, (float)b2_, (float)eps_, nullptr, (int)(t_ + 1), (float)scale};
+                 lr, (float)b1_, (float)b2_, (float)eps_, nullptr, (int)(t_ + 1), (float)scale};
       adam_apply(a, s_);
     } else {
       SgdArgs a{(float*)params_.data_ptr(), opt_ >= 2 ? (float*)m_.data_ptr() : nullptr, g, nullptr, nullptr, n_,
-                (float)lr_, opt_ >= 2 ? (float)mom_ : 0.f, 0.f, (float)scale, opt_ == 3 ? 1 : 0};
+                lr, opt_ >= 2 ? (float)mom_ : 0.f, 0.f, (float)scale, opt_ == 3 ? 1 : 0, nullptr, 0};
       sgd_apply(a, s_);
     }
     ++t_;
@@ -220,8 +239,9 @@ class GpuPsShard : public torch::CustomClassHolder {
   }
 
   int64_t device_, total_, nw_, opt_;
-  double lr_, b1_, b2_, eps_, mom_;
+  double b1_, b2_, eps_, mom_;
   bool sync_;
+  LrSchedule sched_;
   int64_t n_ = 0, slot_ = 0, t_ = 0;
   bool copy_kernel_ = true;
   std::vector<std::pair<int64_t, int64_t>> ranges_;
@@ -298,10 +318,13 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def(torch::init<int64_t, at::Tensor, int64_t, int64_t, int64_t, double, double, double, double, double, bool>())
       .def("numel", &GpuPsShard::numel)
       .def("updates", &GpuPsShard::updates)
+      .def("set_lr_schedule", &GpuPsShard::set_lr_schedule)
+      .def("current_lr", &GpuPsShard::current_lr)
       .def("params", &GpuPsShard::params)
       .def("slot_m", &GpuPsShard::slot_m)
       .def("slot_v", &GpuPsShard::slot_v)
       .def("mailbox", &GpuPsShard::mailbox)
+      .def("test_mailbox_slot", &GpuPsShard::test_mailbox_slot)
       .def("open_worker", &GpuPsShard::open_worker)
       .def("pull_init", &GpuPsShard::pull_init)
       .def("load_state", &GpuPsShard::load_state)

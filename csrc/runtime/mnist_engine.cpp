@@ -150,11 +150,28 @@ class MnistEngine : public torch::CustomClassHolder {
   }
 
   void set_adam(double lr, double b1, double b2, double eps) {
-    opt_ = 0; lr_ = lr; b1_ = b1; b2_ = b2; eps_ = eps;
+    opt_ = 0; b1_ = b1; b2_ = b2; eps_ = eps;
+    sched_ = lr_constant((float)lr);
   }
   void set_momentum(double lr, double momentum, bool nesterov) {
-    opt_ = momentum > 0 ? 2 : 1; lr_ = lr; momentum_ = momentum; nesterov_ = nesterov;
+    opt_ = momentum > 0 ? 2 : 1; momentum_ = momentum; nesterov_ = nesterov;
+    sched_ = lr_constant((float)lr);
   }
+  // Learning rate as a function of global_step (csrc/lr_schedule.h), evaluated by the optimizer
+  // kernels from the device step counter: a captured multi-step graph follows it with no host round
+  // trip. kind: constant | exponential | piecewise | polynomial | cosine; params = {lr, decay_steps,
+  // rate, end, power, alpha, warmup_steps, staircase}. set_adam / set_momentum reset it to constant.
+  // Like every optimizer setting it is baked into graphs captured before the call: capture again.
+  void set_lr_schedule(std::string kind, std::vector<double> params, std::vector<int64_t> boundaries,
+                       std::vector<double> values) {
+    try {
+      sched_ = make_lr_schedule(kind, params, boundaries, values);
+    } catch (const std::invalid_argument& e) {
+      TORCH_CHECK(false, e.what());
+    }
+  }
+  // lr the update from global_step = s uses (host evaluation of the same function)
+  double lr_at_step(int64_t s) const { return (double)lr_at(sched_, s); }
   void set_comm(c10::intrusive_ptr<RcclComm> comm, bool bf16_grads) {
     comm_ = comm;
     bf16_comm_ = bf16_grads && !fp32_;
@@ -330,14 +347,15 @@ class MnistEngine : public torch::CustomClassHolder {
     const int64_t n = end - beg;
     if (opt_ == 0) {
       AdamArgs a{(float*)params_.data_ptr() + beg, (float*)m_.data_ptr() + beg, (float*)v_.data_ptr() + beg,
-                 (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, (float)lr_,
+                 (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, sched_,
                  (float)b1_, (float)b2_, (float)eps_, tsrc ? tsrc : (const int64_t*)step_.data_ptr(), t_offset,
                  (float)grad_scale};
       adam_apply(a, s);
     } else {
       SgdArgs a{(float*)params_.data_ptr() + beg, opt_ == 2 ? (float*)m_.data_ptr() + beg : nullptr,
-                (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, (float)lr_,
-                (float)momentum_, 0.f, (float)grad_scale, nesterov_ ? 1 : 0};
+                (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, sched_,
+                (float)momentum_, 0.f, (float)grad_scale, nesterov_ ? 1 : 0,
+                tsrc ? tsrc : (const int64_t*)step_.data_ptr(), t_offset};
       sgd_apply(a, s);
     }
   }
@@ -376,7 +394,7 @@ class MnistEngine : public torch::CustomClassHolder {
     const bool fused = opt_ == 0 && fuse_tail_;
     if (fused) a.t_out = (int64_t*)tnext_.data_ptr();
     MnistAdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
-                    (uint16_t*)pbf_.data_ptr(), (float)lr_, (float)b1_, (float)b2_, (float)eps_,
+                    (uint16_t*)pbf_.data_ptr(), sched_, (float)b1_, (float)b2_, (float)eps_,
                     (const int64_t*)tnext_.data_ptr(), (int64_t*)step_.data_ptr(), nullptr};
     // bf16 fc-region gradients (the DP wire format): the fc backward writes 2 B and Adam reads
     // 2 B per gradient instead of 4 + 4 (13 MB less HBM traffic per step)
@@ -576,7 +594,7 @@ class MnistEngine : public torch::CustomClassHolder {
         const int64_t n[3] = {end[0] - beg[0], end[1] - beg[1], end[2] - beg[2]};
         AdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
                    (const float*)grad_.data_ptr(), (uint16_t*)pbf_.data_ptr(),
-                   bf16_comm_ ? (const uint16_t*)gbf_.data_ptr() : nullptr, 0, (float)lr_, (float)b1_, (float)b2_,
+                   bf16_comm_ ? (const uint16_t*)gbf_.data_ptr() : nullptr, 0, sched_, (float)b1_, (float)b2_,
                    (float)eps_, t, 0, (float)scale};
         if (split_opt) {
           adam_apply_ranges(o, 2, beg + 1, n + 1, s);
@@ -651,7 +669,7 @@ class MnistEngine : public torch::CustomClassHolder {
       // no bf16 shadow: nothing in fp32 mode reads it (set_dtype("bf16") re-derives it), and its
       // 6.5 MB of writes are 1 us of the bandwidth-bound optimizer tail
       MnistAdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
-                      nullptr, (float)lr_, (float)b1_, (float)b2_, (float)eps_,
+                      nullptr, sched_, (float)b1_, (float)b2_, (float)eps_,
                       (const int64_t*)tnext_.data_ptr(), (int64_t*)step_.data_ptr(), nullptr};
       mark(P_BCONV, s);
       mnist_adam_fused(r, o, s, true);
@@ -1158,7 +1176,8 @@ class MnistEngine : public torch::CustomClassHolder {
   int fc1_splits_, wg2_splits_;
   int64_t input_mode_ = 0;
   int opt_ = 0;
-  double lr_ = 0.01, b1_ = 0.9, b2_ = 0.999, eps_ = 1e-8, momentum_ = 0.0;
+  double b1_ = 0.9, b2_ = 0.999, eps_ = 1e-8, momentum_ = 0.0;
+  LrSchedule sched_ = lr_constant(0.01f);
   bool nesterov_ = false;
   bool bf16_comm_ = true;
   c10::intrusive_ptr<RcclComm> comm_;
@@ -1242,6 +1261,8 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)
       .def("set_momentum", &MnistEngine::set_momentum)
+      .def("set_lr_schedule", &MnistEngine::set_lr_schedule)
+      .def("lr_at_step", &MnistEngine::lr_at_step)
       .def("set_comm", &MnistEngine::set_comm)
       .def("set_ipc", &MnistEngine::set_ipc)
       .def("set_ipc_gather", &MnistEngine::set_ipc_gather)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "lr_schedule.h"
+
 namespace tfd {
 
 // ---------------- fused MNIST CNN train step ----------------
@@ -84,7 +86,8 @@ void mnist_conv_grad_reduce(const MnistStepArgs& a, hipStream_t s);
 struct MnistAdamArgs {
   float* p; float* m; float* v;
   uint16_t* pbf;  // bf16 shadow written beside p; null: none (the fp32 engine reads p itself)
-  float lr, beta1, beta2, eps;
+  LrSchedule sched;  // lr = lr_at(sched, *t - 1), evaluated where t is consumed
+  float beta1, beta2, eps;
   const int64_t* t;
   int64_t* step;
   const uint16_t* gbf;  // if non-null: the fc-region (bucket A) gradients are bf16 here (gbf_a)
@@ -137,7 +140,8 @@ struct AdamArgs {
   float* p; float* m; float* v; const float* g; uint16_t* pbf;
   const uint16_t* gbf;         // if non-null, gradients are read from this bf16 buffer instead of g
   int64_t n;
-  float lr, beta1, beta2, eps;
+  LrSchedule sched;            // lr = lr_at(sched, t - 1): global_step before this update (lr_schedule.h)
+  float beta1, beta2, eps;
   const int64_t* step;         // device step counter; Adam's t = *step + t_offset (read-only here)
   int t_offset;
   float grad_scale;            // multiply g (e.g. 1/N for sum-all-reduce)
@@ -149,7 +153,10 @@ void adam_apply(const AdamArgs& a, hipStream_t s);
 void adam_apply_ranges(const AdamArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s);
 struct SgdArgs {
   float* p; float* mom; const float* g; uint16_t* pbf; const uint16_t* gbf; int64_t n;
-  float lr, momentum, weight_decay, grad_scale; int nesterov;
+  LrSchedule sched;            // lr = lr_at(sched, t - 1), t = *step + t_offset as in AdamArgs
+  float momentum, weight_decay, grad_scale; int nesterov;
+  const int64_t* step;         // read only when the schedule is not constant; null: 0
+  int t_offset;
 };
 // roofline probes: the optimizer's byte floor (Adam's 28 B/param of traffic, optional extra fp32 read
 // stream of nx4 float4) and an empty launch (tools/debug/roofline_probe.py)
@@ -157,6 +164,8 @@ void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf
                   int blocks, int unroll, hipStream_t s);
 void noop_launch(int blocks, hipStream_t s);
 void sgd_apply(const SgdArgs& a, hipStream_t s);
+// debug probe: out[i] = lr_at(sc, steps[i]) through the device function (one block)
+void lr_schedule_eval(const LrSchedule& sc, const int64_t* steps, float* out, int64_t n, hipStream_t s);
 void cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s);
 void cast_bf16_f32(const uint16_t* x, float* y, int64_t n, float scale, hipStream_t s);
 void scale_f32(float* x, int64_t n, float scale, hipStream_t s);

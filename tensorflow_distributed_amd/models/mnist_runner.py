@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..training.optimizers import FlatApplier, base_optimizer
+from ..training.optimizers import FlatApplier, base_optimizer, is_schedule, lr_at, schedule_args
 from . import mnist_cnn as M
 
 
@@ -38,6 +38,13 @@ def _as_f32(x) -> torch.Tensor:
 class MnistRunnerBase:
     batch_size: int
     device: torch.device
+
+    def current_lr(self) -> float:
+        """Learning rate of the NEXT update, from the host's mirror of global_step (no device read)."""
+        step = getattr(self, "_hstep", None)
+        if step is None:
+            step = self.global_step()
+        return lr_at(self.opt.learning_rate, step)
 
     # -- state (flat layout) --
     def params(self) -> torch.Tensor: ...
@@ -213,12 +220,16 @@ class NativeMnistRunner(MnistRunnerBase):
         self.eng = torch.classes.tfd.MnistEngine(batch_size, self.device.index, keep_prob, seed, rank)
         self.eng.set_dtype(dtype)  # "bf16" MFMA operands, or "fp32" (the reference's precision)
         o = self.opt
+        lr0 = lr_at(o.learning_rate, 0)
         if o.kind == "adam":
-            self.eng.set_adam(o.learning_rate, o.beta1, o.beta2, o.epsilon)
+            self.eng.set_adam(lr0, o.beta1, o.beta2, o.epsilon)
         elif o.kind == "momentum":
-            self.eng.set_momentum(o.learning_rate, o.momentum, o.use_nesterov)
+            self.eng.set_momentum(lr0, o.momentum, o.use_nesterov)
         else:
-            self.eng.set_momentum(o.learning_rate, 0.0, False)
+            self.eng.set_momentum(lr0, 0.0, False)
+        if is_schedule(o.learning_rate):
+            # evaluated by the optimizer kernels from the device global_step (csrc/lr_schedule.h)
+            self.eng.set_lr_schedule(*schedule_args(o.learning_rate))
         self.comm = comm
         if comm is not None:
             self.eng.set_comm(comm, bf16_grads)
@@ -235,6 +246,15 @@ class NativeMnistRunner(MnistRunnerBase):
 
     # ---- observability ----
     PHASES = ("fwd_ms", "bwd_fc_ms", "bwd_conv_ms", "optim_ms", "allreduce_ms", "comm_wait_ms", "step_ms_gpu")
+
+    def set_lr_schedule(self, learning_rate) -> None:
+        """Replace the learning rate (a float or a schedule from ``training.optimizers``). Like the
+        phase timing it is baked into captured graphs: the next step captures again."""
+        import dataclasses
+
+        self.opt = dataclasses.replace(self.opt, learning_rate=learning_rate)
+        self.eng.set_lr_schedule(*schedule_args(learning_rate))
+        self._graph_ready = False
 
     def set_phase_timing(self, on: bool = True) -> None:
         """HIP timing events at the step's phase boundaries (recorded inside the captured graph too).

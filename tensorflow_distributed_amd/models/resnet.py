@@ -24,6 +24,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from ..training.optimizers import is_schedule, lr_at, schedule_args
+
 ops = None
 
 
@@ -950,8 +952,25 @@ class ResNet:
         loss_rows, correct, _ = ops.softmax_xent(logits.contiguous(), labels)
         return float(loss_rows.float().sum().item()), int(round(float(correct.float().sum().item())))
 
-    def train_step(self, x, labels, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4):
-        """fwd + bwd (bucketed all-reduce overlapped) + fused flat SGD-momentum. Returns loss tensor."""
+    @staticmethod
+    def lr_op_args(lr, momentum, weight_decay, scale, global_step, step_tensor=None):
+        """The arguments of ``tfd::momentum_flat`` after ``pbf``: a schedule with a device step tensor
+        goes to the kernel whole (``t_offset = 1``: the tensor holds the step count before the update);
+        otherwise the rate is ``lr_at(lr, global_step)``, evaluated here on the host."""
+        if step_tensor is not None and is_schedule(lr):
+            kind, params, bounds, values = schedule_args(lr)
+            return (params[0], momentum, weight_decay, False, scale, step_tensor, 1, kind, params, bounds, values)
+        return (lr_at(lr, global_step), momentum, weight_decay, False, scale)
+
+    def train_step(self, x, labels, lr=0.1, momentum: float = 0.9, weight_decay: float = 1e-4,
+                   global_step: int = 0, step_tensor: Optional[torch.Tensor] = None):
+        """fwd + bwd (bucketed all-reduce overlapped) + fused flat SGD-momentum. Returns loss tensor.
+
+        ``lr``: a float, or a learning-rate schedule (training/optimizers.py). A schedule is evaluated
+        on the host at ``global_step`` (the step count before this update), or -- when ``step_tensor``
+        (an int64 device scalar holding that count) is given, the captured-graph case -- by the
+        optimizer kernel from the tensor, so a replayed graph follows the schedule; the caller
+        advances the tensor between steps."""
         self.reducer.reset()
         # one fill of the flat fp32 grad buffer instead of a memset per split-K weight gradient
         self.fp.grad.zero_()
@@ -969,8 +988,8 @@ class ResNet:
             self.grads_zeroed = False
         self.reducer.finish()
         scale = 1.0 / self.reducer.world
-        _ops().momentum_flat(self.fp.master, self.fp.momentum, self.reducer.reduced_grads(), self.fp.shadow, lr,
-                             momentum, weight_decay, False, scale)
+        _ops().momentum_flat(self.fp.master, self.fp.momentum, self.reducer.reduced_grads(), self.fp.shadow,
+                             *self.lr_op_args(lr, momentum, weight_decay, scale, global_step, step_tensor))
         return loss.detach()
 
 
@@ -995,8 +1014,9 @@ class ResNetRunner:
     def params(self) -> torch.Tensor:
         return self.m.fp.master
 
-    def train_step(self, x, labels, lr: float, **kw):
-        loss = self.m.train_step(x, labels, lr=lr, **kw)
+    def train_step(self, x, labels, lr, **kw):
+        """``lr``: a float or a schedule, evaluated at this runner's ``global_step``."""
+        loss = self.m.train_step(x, labels, lr=lr, global_step=self._step, **kw)
         self._step += 1
         return loss
 

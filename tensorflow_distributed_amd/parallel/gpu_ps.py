@@ -43,7 +43,9 @@ def _opt_args(opt):
     kind = OPT_KIND[opt.kind]
     if opt.kind == "momentum" and getattr(opt, "use_nesterov", False):
         kind = 3
-    return (kind, float(opt.learning_rate), float(getattr(opt, "beta1", 0.9)), float(getattr(opt, "beta2", 0.999)),
+    from ..training.optimizers import lr_at
+
+    return (kind, lr_at(opt.learning_rate, 0), float(getattr(opt, "beta1", 0.9)), float(getattr(opt, "beta2", 0.999)),
             float(getattr(opt, "epsilon", 1e-8)), float(getattr(opt, "momentum", 0.0)))
 
 
@@ -53,7 +55,7 @@ class GpuParameterServerService:
     def __init__(self, ps_index: int, num_ps: int, num_workers: int, layout: ShardLayout, optimizer,
                  device: torch.device, sync: bool = False, replicas_to_aggregate: Optional[int] = None):
         from .. import _native
-        from ..training.optimizers import base_optimizer
+        from ..training.optimizers import base_optimizer, is_schedule, schedule_args
 
         _native.require()
         self.ps = ps_index
@@ -67,6 +69,9 @@ class GpuParameterServerService:
 
         self.shard = torch.classes.tfd.GpuPsShard(device.index, _ranges_tensor(layout, ps_index), M.TOTAL,
                                                   num_workers, *_opt_args(self.opt), bool(sync))
+        if is_schedule(self.opt.learning_rate):
+            # evaluated per update from the shard's own update count, like TF's per-PS beta powers
+            self.shard.set_lr_schedule(*schedule_args(self.opt.learning_rate))
         self.n = layout.sizes[ps_index]
         self.slot_elems = (max(self.n, 4) + 3) // 4 * 4
         self.global_step = 0

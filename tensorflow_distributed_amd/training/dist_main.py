@@ -51,6 +51,23 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_integer("train_steps", 4, "Number of (global) training steps to perform")
     f.DEFINE_integer("batch_size", 128, "Training batch size")
     f.DEFINE_float("learning_rate", 0.01, "Learning rate")
+    # learning-rate schedule over global_step (training/optimizers.py; evaluated on the device by the
+    # optimizer kernels, csrc/lr_schedule.h). The defaults are the constant --learning_rate.
+    f.DEFINE_enum("lr_schedule", "constant", ["constant", "exponential", "piecewise", "polynomial", "cosine"],
+                  "Learning rate as a function of global_step: constant = --learning_rate; exponential = "
+                  "lr * rate^(step / decay_steps) (tf.train.exponential_decay); piecewise = --lr_values between "
+                  "--lr_boundaries (tf.train.piecewise_constant); polynomial = (lr - end) * (1 - step/decay_steps)"
+                  "^power + end; cosine = lr * ((1 - alpha) * 0.5 * (1 + cos(pi * step/decay_steps)) + alpha)")
+    f.DEFINE_integer("lr_decay_steps", 1000, "--lr_schedule exponential / polynomial / cosine: decay steps")
+    f.DEFINE_float("lr_decay_rate", 0.96, "--lr_schedule=exponential: decay rate")
+    f.DEFINE_boolean("lr_staircase", False, "--lr_schedule=exponential: integer step / decay_steps")
+    f.DEFINE_string("lr_boundaries", "", "--lr_schedule=piecewise: comma-separated increasing global steps (at most 4); "
+                    "the rate is values[i] for the first i with step <= boundaries[i]")
+    f.DEFINE_string("lr_values", "", "--lr_schedule=piecewise: comma-separated rates, one more than boundaries")
+    f.DEFINE_float("lr_end", 0.0001, "--lr_schedule=polynomial: end learning rate")
+    f.DEFINE_float("lr_power", 1.0, "--lr_schedule=polynomial: power")
+    f.DEFINE_float("lr_alpha", 0.0, "--lr_schedule=cosine: floor, as a fraction of --learning_rate")
+    f.DEFINE_integer("lr_warmup_steps", 0, "Linear warm-up: for step < this, the rate is scaled by (step + 1) / this")
     f.DEFINE_boolean("sync_replicas", True, "Use the sync_replicas (synchronized replicas) mode, "
                      "wherein the parameter updates from workers are aggregated before applied to "
                      "avoid stale gradients")
@@ -131,14 +148,33 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "by a per-epoch shuffle (no per-step host feed); False = host next_batch + H2D per step")
 
 
+def _make_learning_rate():
+    """--learning_rate, or the schedule the --lr_* flags describe (a float when they are all default)."""
+    from . import optimizers as O
+
+    lr, w, kind = FLAGS.learning_rate, FLAGS.lr_warmup_steps, FLAGS.lr_schedule
+    if kind == "exponential":
+        return O.ExponentialDecay(lr, FLAGS.lr_decay_steps, FLAGS.lr_decay_rate, FLAGS.lr_staircase, w)
+    if kind == "piecewise":
+        bounds = tuple(int(b) for b in FLAGS.lr_boundaries.split(",") if b.strip())
+        values = tuple(float(v) for v in FLAGS.lr_values.split(",") if v.strip())
+        return O.PiecewiseConstant(bounds, values, w)
+    if kind == "polynomial":
+        return O.PolynomialDecay(lr, FLAGS.lr_decay_steps, FLAGS.lr_end, FLAGS.lr_power, w)
+    if kind == "cosine":
+        return O.CosineDecay(lr, FLAGS.lr_decay_steps, FLAGS.lr_alpha, w)
+    return O.ConstantWarmup(lr, w) if w > 0 else lr
+
+
 def _make_optimizer():
     from .optimizers import AdamOptimizer, GradientDescentOptimizer, MomentumOptimizer
 
+    lr = _make_learning_rate()
     if FLAGS.optimizer == "sgd":
-        return GradientDescentOptimizer(FLAGS.learning_rate)
+        return GradientDescentOptimizer(lr)
     if FLAGS.optimizer == "momentum":
-        return MomentumOptimizer(FLAGS.learning_rate, FLAGS.momentum)
-    return AdamOptimizer(FLAGS.learning_rate)
+        return MomentumOptimizer(lr, FLAGS.momentum)
+    return AdamOptimizer(lr)
 
 
 def host_identity() -> str:
@@ -261,8 +297,10 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
     print("Training begins @ %f" % time_begin)
     local_step = 0
     step = runner.global_step()
+    learning_rate = _make_learning_rate()  # a float or a schedule of the runner's global_step
+    runner.learning_rate = learning_rate   # the Supervisor's learning_rate summary scalar
     while step < FLAGS.train_steps:
-        loss = runner.train_step(x, y, lr=FLAGS.learning_rate)
+        loss = runner.train_step(x, y, lr=learning_rate)
         step = runner.global_step()
         local_step += 1
         if not FLAGS.quiet:
@@ -460,6 +498,9 @@ def main(argv=None) -> int:
     server = Server(cluster, job_name=FLAGS.job_name, task_index=FLAGS.task_index,
                     existing_servers=FLAGS.existing_servers, timeout_s=FLAGS.rendezvous_timeout)
     opt = _make_optimizer()
+    from .optimizers import lr_at
+
+    learning_rate = opt.learning_rate  # a float, or a schedule of global_step
     layout = async_ps.mnist_layout(cluster.num_ps) if cluster.num_ps else None
     if not FLAGS.sync_replicas and layout is None:
         raise ValueError("--sync_replicas=False (async parameter-server mode) needs at least one --ps_hosts task")
@@ -727,6 +768,11 @@ def main(argv=None) -> int:
         if metrics.path:
             rec = dict(step=local_step, global_step=step, step_ms=1e3 * (now - t0), loss=runner.last_loss(),
                        images_per_sec=FLAGS.batch_size * (num_workers if sync else 1) / max(now - t0, 1e-9))
+            if not ps_mode:
+                # lr of the update that produced this global step, from the host's step mirror (no device
+                # read). Not logged in the parameter-server modes: there every ps shard evaluates the
+                # schedule at its own update count, which is not this worker's global step
+                rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
             if phase_timing:
                 ph = runner.phase_times()
                 rec.update(ph)
@@ -761,7 +807,7 @@ def main(argv=None) -> int:
             acc = 100.0 * sum(accs) / len(accs)
             eval_time += time.time() - te
             row = dict(steps=eval_at.pop(0), time=time.time() - time_begin - eval_time, accuracy=round(acc, 2),
-                       lr=FLAGS.learning_rate)
+                       lr=lr_at(learning_rate, step))
             perf_rows.append(row)
             print("Performance row: %d %.1f %.2f %g" % (row["steps"], row["time"], row["accuracy"], row["lr"]))
             metrics.log(event="performance", **row)

@@ -16,19 +16,166 @@ Two layers:
 TF ApplyAdam: ``lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)``; ``m = m + (g - m)(1 - b1)``;
 ``v = v + (g^2 - v)(1 - b2)``; ``p -= lr_t * m / (sqrt(v) + eps)``, ``t`` = update count (the
 ``beta1_power``/``beta2_power`` accumulators are ``b^t``).
+
+Learning-rate schedules (``tf.train.exponential_decay`` / ``piecewise_constant`` /
+``polynomial_decay`` / ``cosine_decay``, each with an optional linear warm-up): the ``learning_rate``
+of every optimizer config is a float or one of the schedule dataclasses below. A schedule is a
+function of ``global_step`` *before* the update (Adam's ``t - 1``), which is what TF's graph reads.
+:func:`lr_at` is the fp64 definition; the GPU kernels evaluate the same formulas in fp32 from the
+device step counter (``csrc/lr_schedule.h``), so a captured step graph follows the schedule.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import Optional, Tuple, Union
 
 import torch
+
+MAX_BOUNDARIES = 4  # csrc/lr_schedule.h: kLrMaxBoundaries
+
+
+def _check_common(decay_steps, warmup_steps) -> None:
+    if int(decay_steps) != decay_steps or decay_steps < 1:
+        raise ValueError(f"decay_steps must be an integer >= 1, got {decay_steps!r}")
+    if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+        raise ValueError(f"warmup_steps must be an integer >= 0, got {warmup_steps!r}")
+
+
+@dataclass(frozen=True)
+class ExponentialDecay:
+    """``lr * rate ** (s / decay_steps)``; ``staircase``: the integer quotient ``s // decay_steps``."""
+    learning_rate: float
+    decay_steps: int
+    decay_rate: float
+    staircase: bool = False
+    warmup_steps: int = 0
+    kind = "exponential"
+
+    def __post_init__(self):
+        _check_common(self.decay_steps, self.warmup_steps)
+
+
+@dataclass(frozen=True)
+class PiecewiseConstant:
+    """``values[i]`` for the first ``i`` with ``s <= boundaries[i]``, else ``values[-1]`` (TF's
+    inclusive convention). At most 4 boundaries; values are absolute rates."""
+    boundaries: Tuple[int, ...]
+    values: Tuple[float, ...]
+    warmup_steps: int = 0
+    kind = "piecewise"
+
+    def __post_init__(self):
+        b = tuple(self.boundaries)
+        v = tuple(float(x) for x in self.values)
+        if any(int(x) != x for x in b):
+            raise ValueError(f"boundaries must be integer steps, got {b!r}")
+        b = tuple(int(x) for x in b)
+        if len(b) > MAX_BOUNDARIES:
+            raise ValueError(f"at most {MAX_BOUNDARIES} boundaries, got {len(b)}")
+        if len(v) != len(b) + 1:
+            raise ValueError(f"len(values) must be len(boundaries) + 1, got {len(v)} values for {len(b)} boundaries")
+        if any(b[i] <= b[i - 1] for i in range(1, len(b))):
+            raise ValueError(f"boundaries must be strictly increasing, got {b!r}")
+        _check_common(1, self.warmup_steps)
+        object.__setattr__(self, "boundaries", b)
+        object.__setattr__(self, "values", v)
+
+    @property
+    def learning_rate(self) -> float:
+        return self.values[0]
+
+
+@dataclass(frozen=True)
+class PolynomialDecay:
+    """``(lr - end) * (1 - min(s, decay_steps) / decay_steps) ** power + end``."""
+    learning_rate: float
+    decay_steps: int
+    end_learning_rate: float = 0.0001
+    power: float = 1.0
+    warmup_steps: int = 0
+    kind = "polynomial"
+
+    def __post_init__(self):
+        _check_common(self.decay_steps, self.warmup_steps)
+
+
+@dataclass(frozen=True)
+class CosineDecay:
+    """``lr * ((1 - alpha) * 0.5 * (1 + cos(pi * min(s, decay_steps) / decay_steps)) + alpha)``."""
+    learning_rate: float
+    decay_steps: int
+    alpha: float = 0.0
+    warmup_steps: int = 0
+    kind = "cosine"
+
+    def __post_init__(self):
+        _check_common(self.decay_steps, self.warmup_steps)
+
+
+@dataclass(frozen=True)
+class ConstantWarmup:
+    """A constant rate behind a linear warm-up (``--lr_schedule=constant --lr_warmup_steps=w``)."""
+    learning_rate: float
+    warmup_steps: int
+    kind = "constant"
+
+    def __post_init__(self):
+        _check_common(1, self.warmup_steps)
+
+
+SCHEDULES = (ExponentialDecay, PiecewiseConstant, PolynomialDecay, CosineDecay, ConstantWarmup)
+LearningRate = Union[float, ExponentialDecay, PiecewiseConstant, PolynomialDecay, CosineDecay, ConstantWarmup]
+
+
+def is_schedule(lr) -> bool:
+    return isinstance(lr, SCHEDULES)
+
+
+def lr_at(lr: LearningRate, step: int) -> float:
+    """The learning rate of the update that starts from ``global_step == step`` (fp64)."""
+    if not is_schedule(lr):
+        return float(lr)
+    s = int(step)
+    if isinstance(lr, PiecewiseConstant):
+        out = lr.values[-1]
+        for b, v in zip(lr.boundaries, lr.values):
+            if s <= b:
+                out = v
+                break
+    elif isinstance(lr, ExponentialDecay):
+        e = (s // lr.decay_steps) if lr.staircase else s / lr.decay_steps
+        out = lr.learning_rate * lr.decay_rate ** e
+    elif isinstance(lr, PolynomialDecay):
+        f = min(s, lr.decay_steps) / lr.decay_steps
+        out = (lr.learning_rate - lr.end_learning_rate) * (1.0 - f) ** lr.power + lr.end_learning_rate
+    elif isinstance(lr, CosineDecay):
+        f = min(s, lr.decay_steps) / lr.decay_steps
+        out = lr.learning_rate * ((1.0 - lr.alpha) * 0.5 * (1.0 + math.cos(math.pi * f)) + lr.alpha)
+    else:
+        out = lr.learning_rate
+    if s < lr.warmup_steps:
+        out *= (s + 1) / lr.warmup_steps
+    return float(out)
+
+
+def schedule_args(lr: LearningRate):
+    """``(kind, params, boundaries, values)`` as the native ``set_lr_schedule`` / flat ops take them:
+    params = [lr, decay_steps, rate, end, power, alpha, warmup_steps, staircase]."""
+    if not is_schedule(lr):
+        return "constant", [float(lr)], [], []
+    p = [float(lr.learning_rate), float(getattr(lr, "decay_steps", 1)), float(getattr(lr, "decay_rate", 1.0)),
+         float(getattr(lr, "end_learning_rate", 0.0)), float(getattr(lr, "power", 1.0)), float(getattr(lr, "alpha", 0.0)),
+         float(lr.warmup_steps), float(bool(getattr(lr, "staircase", False)))]
+    if isinstance(lr, PiecewiseConstant):
+        return lr.kind, p, list(lr.boundaries), list(lr.values)
+    return lr.kind, p, [], []
 
 
 @dataclass
 class AdamOptimizer:
-    learning_rate: float = 0.001
+    learning_rate: LearningRate = 0.001
     beta1: float = 0.9
     beta2: float = 0.999
     epsilon: float = 1e-8
@@ -38,14 +185,14 @@ class AdamOptimizer:
 
 @dataclass
 class GradientDescentOptimizer:
-    learning_rate: float = 0.01
+    learning_rate: LearningRate = 0.01
     name: str = "GradientDescent"
     kind: str = field(default="sgd", init=False)
 
 
 @dataclass
 class MomentumOptimizer:
-    learning_rate: float = 0.01
+    learning_rate: LearningRate = 0.01
     momentum: float = 0.9
     use_nesterov: bool = False
     name: str = "Momentum"
@@ -98,21 +245,22 @@ class FlatApplier:
     def apply(self, p: torch.Tensor, g: torch.Tensor, scale: float = 1.0) -> None:
         o = self.opt
         g = g if scale == 1.0 else g * scale
+        lr = lr_at(o.learning_rate, self.t)  # global_step before this update
         self.t += 1
         if o.kind == "adam":
             b1, b2 = o.beta1, o.beta2
-            lr_t = o.learning_rate * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
+            lr_t = lr * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
             self.m.add_(g - self.m, alpha=1 - b1)
             self.v.add_(g * g - self.v, alpha=1 - b2)
             p.sub_(lr_t * self.m / (self.v.sqrt() + o.epsilon))
         elif o.kind == "momentum":
             self.m.mul_(o.momentum).add_(g)
             if o.use_nesterov:
-                p.sub_(o.learning_rate * (g + o.momentum * self.m))
+                p.sub_(lr * (g + o.momentum * self.m))
             else:
-                p.sub_(o.learning_rate * self.m)
+                p.sub_(lr * self.m)
         else:
-            p.sub_(o.learning_rate * g)
+            p.sub_(lr * g)
 
     def slots(self) -> "OrderedDict[str, torch.Tensor]":
         out = OrderedDict()

@@ -103,10 +103,23 @@ class Supervisor:
         now = time.time()
         t0, s0 = self._last_summary
         vals = dict(scalars or {})
+        lr = self._learning_rate(global_step)
+        if lr is not None:
+            vals.setdefault("learning_rate", lr)
         if now > t0:
             vals["global_step/sec"] = (global_step - s0) / (now - t0)
         self.writer.add_scalars(vals, global_step)
         self._last_summary = (now, global_step)
+
+    def _learning_rate(self, global_step: int) -> Optional[float]:
+        """The schedule's value at ``global_step`` (the rate of the next update), evaluated on the host
+        from the step the caller mirrors: no device read."""
+        from .optimizers import lr_at
+
+        lr = getattr(getattr(self.runner, "opt", None), "learning_rate", None)
+        if lr is None:
+            lr = getattr(self.runner, "learning_rate", None)
+        return None if lr is None else lr_at(lr, global_step)
 
     def save(self, global_step: Optional[int] = None) -> Optional[str]:
         if not (self.is_chief and self.logdir):
