@@ -28,14 +28,9 @@
 #include <vector>
 
 #include "../tfd_kernels.h"
+#include "hip_util.h"
 
 namespace tfd {
-
-#define PS_OK(x)                                                                           \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    TORCH_CHECK(e_ == hipSuccess, #x, " failed: ", hipGetErrorString(e_));                 \
-  } while (0)
 
 namespace {
 
@@ -46,9 +41,9 @@ constexpr int64_t kExportBytes = (int64_t)sizeof(hipIpcMemHandle_t) + 2 * (int64
 at::Tensor export_ptr(void* p, int64_t nbytes) {
   void* base = nullptr;
   size_t size = 0;
-  PS_OK(hipMemGetAddressRange(&base, &size, p));
+  HIP_OK(hipMemGetAddressRange(&base, &size, p));
   hipIpcMemHandle_t h;
-  PS_OK(hipIpcGetMemHandle(&h, base));
+  HIP_OK(hipIpcGetMemHandle(&h, base));
   auto t = at::empty({kExportBytes}, at::TensorOptions().dtype(at::kByte));
   auto* o = (uint8_t*)t.data_ptr();
   std::memcpy(o, &h, sizeof(h));
@@ -72,7 +67,7 @@ struct Mapping {
     std::memcpy(&off, o + sizeof(h), sizeof(off));
     std::memcpy(&nbytes, o + sizeof(h) + sizeof(off), sizeof(nbytes));
     close();
-    PS_OK(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
+    HIP_OK(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
     ptr = (char*)base + off;
   }
   void close() {
@@ -111,8 +106,8 @@ class GpuPsShard : public torch::CustomClassHolder {
     for (auto& r : ranges_) TORCH_CHECK(r.first + r.second <= flat_total, "range past the flat buffer");
     TORCH_CHECK(n_workers >= 1 && n_workers <= 1024, "n_workers");
     TORCH_CHECK(opt >= 0 && opt <= 3, "opt kind");
-    PS_OK(hipSetDevice((int)device));
-    PS_OK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+    HIP_OK(hipSetDevice((int)device));
+    HIP_OK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
     auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
     const int64_t n = std::max<int64_t>(n_, 4);
     params_ = at::zeros({n}, f32);
@@ -121,9 +116,9 @@ class GpuPsShard : public torch::CustomClassHolder {
     if (sync) acc_ = at::zeros({n}, f32);
     // mailbox: its own allocation (exported whole), one fp32 slot per worker, 16-B aligned slots
     slot_ = (n + 3) / 4 * 4;
-    PS_OK(hipMalloc(&mail_, (size_t)nw_ * slot_ * sizeof(float)));
-    PS_OK(hipMemset(mail_, 0, (size_t)nw_ * slot_ * sizeof(float)));
-    PS_OK(hipDeviceSynchronize());
+    HIP_OK(hipMalloc(&mail_, (size_t)nw_ * slot_ * sizeof(float)));
+    HIP_OK(hipMemset(mail_, 0, (size_t)nw_ * slot_ * sizeof(float)));
+    HIP_OK(hipDeviceSynchronize());
     workers_.resize(nw_);
   }
   ~GpuPsShard() override {
@@ -167,10 +162,10 @@ class GpuPsShard : public torch::CustomClassHolder {
   // chief's init: the shard's ranges of worker w's parameters (its engine buffer, peer memory)
   void pull_init(int64_t w, int64_t t) {
     copy_ranges(/*to_worker=*/false, w);
-    PS_OK(hipMemsetAsync(m_.data_ptr(), 0, m_.numel() * sizeof(float), s_));
-    PS_OK(hipMemsetAsync(v_.data_ptr(), 0, v_.numel() * sizeof(float), s_));
-    if (sync_) PS_OK(hipMemsetAsync(acc_.data_ptr(), 0, acc_.numel() * sizeof(float), s_));
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipMemsetAsync(m_.data_ptr(), 0, m_.numel() * sizeof(float), s_));
+    HIP_OK(hipMemsetAsync(v_.data_ptr(), 0, v_.numel() * sizeof(float), s_));
+    if (sync_) HIP_OK(hipMemsetAsync(acc_.data_ptr(), 0, acc_.numel() * sizeof(float), s_));
+    HIP_OK(hipStreamSynchronize(s_));
     t_ = t;
   }
   // restore: values (and slots, when given) in the shard's compact layout, any device
@@ -180,32 +175,32 @@ class GpuPsShard : public torch::CustomClassHolder {
     if (m) slot_m().copy_(*m); else slot_m().zero_();
     if (v) slot_v().copy_(*v); else slot_v().zero_();
     if (sync_) acc_.zero_();
-    PS_OK(hipDeviceSynchronize());
+    HIP_OK(hipDeviceSynchronize());
     t_ = t;
   }
   // async (Hogwild) update with worker w's mailbox gradient: TF ApplyAdam / SGD / Momentum, t += 1
   void apply(int64_t w, double scale) {
     TORCH_CHECK(w >= 0 && w < nw_, "worker index");
     step_with(mail_ + w * slot_, scale);
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipStreamSynchronize(s_));
   }
   // sync (backup workers): acc += mailbox[w]
   void accumulate(int64_t w) {
     TORCH_CHECK(sync_ && w >= 0 && w < nw_, "accumulate: sync shard, worker index");
     vec_accumulate((float*)acc_.data_ptr(), mail_ + w * slot_, n_, 1.f, s_);
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipStreamSynchronize(s_));
   }
   // sync: one averaged update from the accumulator (scale = 1/R), then acc = 0
   void apply_accumulated(double scale) {
     TORCH_CHECK(sync_, "apply_accumulated: sync shard");
     step_with((const float*)acc_.data_ptr(), scale);
-    PS_OK(hipMemsetAsync(acc_.data_ptr(), 0, acc_.numel() * sizeof(float), s_));
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipMemsetAsync(acc_.data_ptr(), 0, acc_.numel() * sizeof(float), s_));
+    HIP_OK(hipStreamSynchronize(s_));
   }
   // the shard's current values -> worker w's engine parameters (its ranges only)
   void push(int64_t w) {
     copy_ranges(/*to_worker=*/true, w);
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipStreamSynchronize(s_));
   }
 
  private:
@@ -233,7 +228,7 @@ class GpuPsShard : public torch::CustomClassHolder {
       char* sp = pb + o * (int64_t)sizeof(float);
       const size_t bytes = (size_t)r.second * sizeof(float);
       if (bytes && copy_kernel_) copy_f32((float*)(to_worker ? wp : sp), (const float*)(to_worker ? sp : wp), r.second, s_);
-      else if (bytes) PS_OK(hipMemcpyAsync(to_worker ? wp : sp, to_worker ? sp : wp, bytes, hipMemcpyDeviceToDevice, s_));
+      else if (bytes) HIP_OK(hipMemcpyAsync(to_worker ? wp : sp, to_worker ? sp : wp, bytes, hipMemcpyDeviceToDevice, s_));
       o += r.second;
     }
   }
@@ -255,8 +250,8 @@ class GpuPsPort : public torch::CustomClassHolder {
  public:
   GpuPsPort(int64_t device, int64_t num_ps) : device_(device), ps_(num_ps), ranges_(num_ps) {
     TORCH_CHECK(num_ps >= 1 && num_ps <= 64, "num_ps");
-    PS_OK(hipSetDevice((int)device));
-    PS_OK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+    HIP_OK(hipSetDevice((int)device));
+    HIP_OK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
   }
   ~GpuPsPort() override {
     for (auto& m : ps_) m.close();
@@ -284,9 +279,9 @@ class GpuPsPort : public torch::CustomClassHolder {
     TORCH_CHECK((w + 1) * sl->second * (int64_t)sizeof(float) <= ps_[p].nbytes, "mailbox slot past the export");
     // the gradient is produced on the caller's stream: order the copies behind it
     hipEvent_t ev;
-    PS_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    PS_OK(hipEventRecord(ev, c10::hip::getCurrentHIPStream().stream()));
-    PS_OK(hipStreamWaitEvent(s_, ev, 0));
+    HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(ev, c10::hip::getCurrentHIPStream().stream()));
+    HIP_OK(hipStreamWaitEvent(s_, ev, 0));
     char* dst = ps_[p].ptr + w * sl->second * (int64_t)sizeof(float);
     const char* src = (const char*)grad.data_ptr();
     int64_t o = 0;
@@ -296,11 +291,11 @@ class GpuPsPort : public torch::CustomClassHolder {
         copy_f32((float*)(dst + o * (int64_t)sizeof(float)), (const float*)(src + r.first * (int64_t)sizeof(float)),
                  r.second, s_);
       else if (r.second)
-        PS_OK(hipMemcpyAsync(dst + o * (int64_t)sizeof(float), src + r.first * (int64_t)sizeof(float),
+        HIP_OK(hipMemcpyAsync(dst + o * (int64_t)sizeof(float), src + r.first * (int64_t)sizeof(float),
                              (size_t)r.second * sizeof(float), hipMemcpyDeviceToDevice, s_));
       o += r.second;
     }
-    PS_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipStreamSynchronize(s_));
     (void)hipEventDestroy(ev);
   }
 

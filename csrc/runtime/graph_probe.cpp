@@ -18,17 +18,13 @@
 
 #include <vector>
 
+#include "hip_util.h"
+
 namespace tfd {
 void probe_add_one(float* p, int64_t n, hipStream_t s);
 void probe_fill(float* p, int64_t n, float v, hipStream_t s);
 
 namespace {
-#define GP_OK(x)                                                                            \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    TORCH_CHECK(e_ == hipSuccess, #x, " failed: ", hipGetErrorString(e_));                  \
-  } while (0)
-
 // info layout (int64): [0] nodes, [1] kernel nodes, [2] memset nodes, [3] other nodes,
 // [4] memset dst - buffer (bytes), [5] memset elementSize, [6] memset width, [7] memset height,
 // [8] memset value, [9] memset node dependency count, [10] elements != 1.0 after the replays,
@@ -38,36 +34,36 @@ at::Tensor memset_capture_probe(at::Tensor buf, int64_t replays, int64_t clear_m
   const int64_t n = buf.numel();
   float* p = (float*)buf.data_ptr();
   hipStream_t s;
-  GP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   probe_fill(p, n, 5.f, s);
-  GP_OK(hipStreamSynchronize(s));
+  HIP_OK(hipStreamSynchronize(s));
   const int cm = (int)(capture_mode & 3);
   const hipStreamCaptureMode mode = cm == 0 ? hipStreamCaptureModeGlobal
                                     : cm == 1 ? hipStreamCaptureModeThreadLocal
                                               : hipStreamCaptureModeRelaxed;
   hipGraph_t g = nullptr;
-  GP_OK(hipStreamBeginCapture(s, mode));
+  HIP_OK(hipStreamBeginCapture(s, mode));
   if (!(capture_mode & 4)) probe_add_one(p, n, s);  // bit 2: the clear is the graph's root node
-  if (clear_mode == 0) GP_OK(hipMemsetAsync(p, 0, n * sizeof(float), s));
-  else if (clear_mode == 1) GP_OK(hipMemsetD32Async((hipDeviceptr_t)p, 0, (size_t)n, s));
+  if (clear_mode == 0) HIP_OK(hipMemsetAsync(p, 0, n * sizeof(float), s));
+  else if (clear_mode == 1) HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p, 0, (size_t)n, s));
   else probe_fill(p, n, 0.f, s);
   probe_add_one(p, n, s);
-  GP_OK(hipStreamEndCapture(s, &g));
+  HIP_OK(hipStreamEndCapture(s, &g));
   std::vector<int64_t> info(14, 0);
   size_t nn = 0;
-  GP_OK(hipGraphGetNodes(g, nullptr, &nn));
+  HIP_OK(hipGraphGetNodes(g, nullptr, &nn));
   std::vector<hipGraphNode_t> nodes(nn);
-  GP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
+  HIP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
   info[0] = (int64_t)nn;
   for (auto nd : nodes) {
     hipGraphNodeType t;
-    GP_OK(hipGraphNodeGetType(nd, &t));
+    HIP_OK(hipGraphNodeGetType(nd, &t));
     if (t == hipGraphNodeTypeKernel) {
       info[1]++;
     } else if (t == hipGraphNodeTypeMemset) {
       info[2]++;
       hipMemsetParams prm{};
-      GP_OK(hipGraphMemsetNodeGetParams(nd, &prm));
+      HIP_OK(hipGraphMemsetNodeGetParams(nd, &prm));
       info[4] = (int64_t)((char*)prm.dst - (char*)p);
       info[5] = prm.elementSize;
       info[6] = (int64_t)prm.width;
@@ -75,24 +71,24 @@ at::Tensor memset_capture_probe(at::Tensor buf, int64_t replays, int64_t clear_m
       info[8] = prm.value;
       info[13] += (int64_t)prm.width * prm.elementSize * std::max<int64_t>(1, (int64_t)prm.height);
       size_t nd_deps = 0;
-      GP_OK(hipGraphNodeGetDependencies(nd, nullptr, &nd_deps));
+      HIP_OK(hipGraphNodeGetDependencies(nd, nullptr, &nd_deps));
       info[9] = (int64_t)nd_deps;
     } else {
       info[3]++;
     }
   }
   hipGraphExec_t ge = nullptr;
-  GP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-  for (int64_t r = 0; r < replays; ++r) GP_OK(hipGraphLaunch(ge, s));
-  GP_OK(hipStreamSynchronize(s));
+  HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+  for (int64_t r = 0; r < replays; ++r) HIP_OK(hipGraphLaunch(ge, s));
+  HIP_OK(hipStreamSynchronize(s));
   std::vector<float> h(n);
-  GP_OK(hipMemcpy(h.data(), p, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(h.data(), p, n * sizeof(float), hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n; ++i) info[10] += h[i] != 1.f;
   info[11] = (int64_t)(h[0] * 1000.f);
   info[12] = (int64_t)(h[n - 1] * 1000.f);
-  GP_OK(hipGraphExecDestroy(ge));
-  GP_OK(hipGraphDestroy(g));
-  GP_OK(hipStreamDestroy(s));
+  HIP_OK(hipGraphExecDestroy(ge));
+  HIP_OK(hipGraphDestroy(g));
+  HIP_OK(hipStreamDestroy(s));
   return at::tensor(info, at::TensorOptions().dtype(at::kLong));
 }
 
@@ -102,21 +98,21 @@ at::Tensor memset_capture_probe(at::Tensor buf, int64_t replays, int64_t clear_m
 at::Tensor graph_memset_nodes(int64_t graph) {
   hipGraph_t g = reinterpret_cast<hipGraph_t>(graph);
   size_t nn = 0;
-  GP_OK(hipGraphGetNodes(g, nullptr, &nn));
+  HIP_OK(hipGraphGetNodes(g, nullptr, &nn));
   std::vector<hipGraphNode_t> nodes(nn);
-  GP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
+  HIP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
   std::vector<int64_t> rows(7, 0);
   rows[0] = (int64_t)nn;
   for (auto nd : nodes) {
     hipGraphNodeType t;
-    GP_OK(hipGraphNodeGetType(nd, &t));
+    HIP_OK(hipGraphNodeGetType(nd, &t));
     if (t == hipGraphNodeTypeKernel) rows[1]++;
     if (t != hipGraphNodeTypeMemset) continue;
     hipMemsetParams prm{};
-    GP_OK(hipGraphMemsetNodeGetParams(nd, &prm));
+    HIP_OK(hipGraphMemsetNodeGetParams(nd, &prm));
     size_t deps = 0, outs = 0;
-    GP_OK(hipGraphNodeGetDependencies(nd, nullptr, &deps));
-    GP_OK(hipGraphNodeGetDependentNodes(nd, nullptr, &outs));
+    HIP_OK(hipGraphNodeGetDependencies(nd, nullptr, &deps));
+    HIP_OK(hipGraphNodeGetDependentNodes(nd, nullptr, &outs));
     const int64_t r[7] = {(int64_t)(uintptr_t)prm.dst, prm.elementSize, (int64_t)prm.width, (int64_t)prm.height,
                           prm.value, (int64_t)deps, (int64_t)outs};
     rows.insert(rows.end(), r, r + 7);
@@ -129,13 +125,13 @@ at::Tensor graph_memset_nodes(int64_t graph) {
 at::Tensor graph_node_types(int64_t graph) {
   hipGraph_t g = reinterpret_cast<hipGraph_t>(graph);
   size_t nn = 0;
-  GP_OK(hipGraphGetNodes(g, nullptr, &nn));
+  HIP_OK(hipGraphGetNodes(g, nullptr, &nn));
   std::vector<hipGraphNode_t> nodes(nn);
-  GP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
+  HIP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
   std::vector<int64_t> counts(16, 0);
   for (auto nd : nodes) {
     hipGraphNodeType t;
-    GP_OK(hipGraphNodeGetType(nd, &t));
+    HIP_OK(hipGraphNodeGetType(nd, &t));
     counts[std::min<int>((int)t, 15)]++;
   }
   return at::tensor(counts, at::TensorOptions().dtype(at::kLong));
@@ -145,7 +141,7 @@ at::Tensor graph_node_types(int64_t graph) {
 // ResNet wgrad took before the fill kernel replaced it)
 void memset_zero_async(at::Tensor buf) {
   TORCH_CHECK(buf.is_cuda() && buf.is_contiguous(), "contiguous GPU buffer");
-  GP_OK(hipMemsetAsync(buf.data_ptr(), 0, buf.nbytes(), c10::hip::getCurrentHIPStream().stream()));
+  HIP_OK(hipMemsetAsync(buf.data_ptr(), 0, buf.nbytes(), c10::hip::getCurrentHIPStream().stream()));
 }
 void atomic_add_one(at::Tensor buf) {
   TORCH_CHECK(buf.is_cuda() && buf.scalar_type() == at::kFloat && buf.is_contiguous(), "fp32 contiguous GPU buffer");

@@ -15,29 +15,24 @@
 #include <algorithm>
 
 #include "../ipc_kernels.h"
+#include "hip_util.h"
 #include "ipc_comm.h"
 
 namespace tfd {
-
-#define HIP_OK2(x)                                                                         \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    TORCH_CHECK(e_ == hipSuccess, #x, " failed: ", hipGetErrorString(e_));                 \
-  } while (0)
 
 IpcComm::IpcComm(int64_t world, int64_t rank, int64_t device, int64_t capacity_elems)
     : world_(world), rank_(rank), device_(device), cap_(capacity_elems) {
   TORCH_CHECK(world >= 1 && world <= kIpcMaxRanks, "IpcComm: world must be in [1, ", kIpcMaxRanks, "]");
   TORCH_CHECK(rank >= 0 && rank < world, "IpcComm: bad rank");
   TORCH_CHECK(capacity_elems > 0, "IpcComm: capacity");
-  HIP_OK2(hipSetDevice((int)device));
+  HIP_OK(hipSetDevice((int)device));
   // two halves of cap_ fp32 (call v stages into half v & 1: double buffering instead of an END barrier)
-  HIP_OK2(hipMalloc(&stage_, 2 * (size_t)cap_ * sizeof(float)));
-  HIP_OK2(hipExtMallocWithFlags(&sig_, kIpcSigInts * sizeof(int), hipDeviceMallocUncached));
-  HIP_OK2(hipMemset(sig_, 0, kIpcSigInts * sizeof(int)));
-  HIP_OK2(hipMemset(stage_, 0, 2 * (size_t)cap_ * sizeof(float)));
-  HIP_OK2(hipDeviceSynchronize());
-  HIP_OK2(hipEventCreateWithFlags(&last_ev_, hipEventDisableTiming));
+  HIP_OK(hipMalloc(&stage_, 2 * (size_t)cap_ * sizeof(float)));
+  HIP_OK(hipExtMallocWithFlags(&sig_, kIpcSigInts * sizeof(int), hipDeviceMallocUncached));
+  HIP_OK(hipMemset(sig_, 0, kIpcSigInts * sizeof(int)));
+  HIP_OK(hipMemset(stage_, 0, 2 * (size_t)cap_ * sizeof(float)));
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipEventCreateWithFlags(&last_ev_, hipEventDisableTiming));
   for (int i = 0; i < kIpcMaxRanks; ++i) {
     peer_stage_[i] = nullptr;
     peer_sig_[i] = nullptr;
@@ -50,8 +45,8 @@ IpcComm::~IpcComm() { close(); }
 
 at::Tensor IpcComm::handle() {
   hipIpcMemHandle_t h[2];
-  HIP_OK2(hipIpcGetMemHandle(&h[0], stage_));
-  HIP_OK2(hipIpcGetMemHandle(&h[1], sig_));
+  HIP_OK(hipIpcGetMemHandle(&h[0], stage_));
+  HIP_OK(hipIpcGetMemHandle(&h[1], sig_));
   auto t = at::empty({2 * (int64_t)sizeof(hipIpcMemHandle_t)}, at::TensorOptions().dtype(at::kByte));
   std::memcpy(t.data_ptr(), h, sizeof(h));
   return t;
@@ -63,13 +58,13 @@ void IpcComm::open(const at::Tensor& all) {
   TORCH_CHECK(all.numel() == world_ * hb && all.scalar_type() == at::kByte, "IpcComm.open: [world, 128] uint8");
   auto c = all.contiguous().cpu();
   const uint8_t* base = c.data_ptr<uint8_t>();
-  HIP_OK2(hipSetDevice((int)device_));
+  HIP_OK(hipSetDevice((int)device_));
   for (int p = 0; p < world_; ++p) {
     if (p == rank_) continue;
     hipIpcMemHandle_t h[2];
     std::memcpy(h, base + p * hb, sizeof(h));
-    HIP_OK2(hipIpcOpenMemHandle(&peer_stage_[p], h[0], hipIpcMemLazyEnablePeerAccess));
-    HIP_OK2(hipIpcOpenMemHandle((void**)&peer_sig_[p], h[1], hipIpcMemLazyEnablePeerAccess));
+    HIP_OK(hipIpcOpenMemHandle(&peer_stage_[p], h[0], hipIpcMemLazyEnablePeerAccess));
+    HIP_OK(hipIpcOpenMemHandle((void**)&peer_sig_[p], h[1], hipIpcMemLazyEnablePeerAccess));
   }
   opened_ = true;
 }
@@ -101,18 +96,18 @@ void IpcComm::close() {
 
 static bool capturing(hipStream_t s) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  HIP_OK2(hipStreamIsCapturing(s, &st));
+  HIP_OK(hipStreamIsCapturing(s, &st));
   return st != hipStreamCaptureStatusNone;
 }
 
 void IpcComm::order(hipStream_t s) {
-  if (last_recorded_ && s != last_stream_ && !capturing(s)) HIP_OK2(hipStreamWaitEvent(s, last_ev_, 0));
+  if (last_recorded_ && s != last_stream_ && !capturing(s)) HIP_OK(hipStreamWaitEvent(s, last_ev_, 0));
 }
 
 void IpcComm::mark(hipStream_t s) {
   last_stream_ = s;
   last_recorded_ = !capturing(s);
-  if (last_recorded_) HIP_OK2(hipEventRecord(last_ev_, s));
+  if (last_recorded_) HIP_OK(hipEventRecord(last_ev_, s));
 }
 
 // Grid of a spinning collective: every block of it must become resident while the peers' blocks
@@ -231,7 +226,7 @@ void IpcComm::all_gather(const at::Tensor& buf) {
 
 int64_t IpcComm::error() {
   int v = 0;
-  HIP_OK2(hipMemcpy(&v, (int*)sig_ + kIpcSigFlags, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&v, (int*)sig_ + kIpcSigFlags, sizeof(int), hipMemcpyDeviceToHost));
   return v;
 }
 

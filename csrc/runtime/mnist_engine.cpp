@@ -1,7 +1,7 @@
 // Native train-step executor for the reference MNIST CNN.
 //
 // Plays the role of the TF1 graph executor + Session.run for the reference's hot loop
-// (/root/reference/mnist_python_m.py:289-302, mnist_single.py:109-117): it owns every device
+// (the reference's mnist_python_m.py:289-302, mnist_single.py:109-117): it owns every device
 // buffer (flat fp32 master params, bf16 shadow, flat grads, Adam slots, activations), sequences
 // the fused HIP kernels of csrc/kernels/mnist.hip, overlaps the bucketed RCCL gradient all-reduce
 // with the conv backward on a second stream, applies the fused flat optimizer, and can capture the
@@ -21,16 +21,11 @@
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
+#include "hip_util.h"
 #include "ipc_comm.h"
 
 namespace tfd {
 using namespace mnist;
-
-#define HIP_OK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    TORCH_CHECK(e_ == hipSuccess, #x, " failed: ", hipGetErrorString(e_));                 \
-  } while (0)
 
 class MnistEngine : public torch::CustomClassHolder {
  public:
@@ -71,31 +66,16 @@ class MnistEngine : public torch::CustomClassHolder {
     ypre_ = at::zeros({B_}, i32);
     ybuf_ = at::zeros({B_}, i32);
     HIP_OK(hipSetDevice((int)device));
-    HIP_OK(hipStreamCreateWithFlags(&comm_stream_, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&ev_a_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_b_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
-    HIP_OK(hipStreamCreateWithFlags(&opt_stream_, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&ev_opt_a_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_start_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_ag_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_p2_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_wag_, hipEventDisableTiming));
-    for (auto& e : pev_) HIP_OK(hipEventCreate(&e));  // timing events (phase timer)
+    // streams and events belong to `device`, so they are created here and not by member initialisers
+    comm_stream_ = HipStream::create();
+    opt_stream_ = HipStream::create();
+    for (HipEvent* e : {&ev_a_, &ev_b_, &ev_done_, &ev_opt_a_, &ev_start_, &ev_ag_, &ev_p2_, &ev_wag_})
+      *e = HipEvent(false);
+    for (auto& e : pev_) e = HipEvent(true);  // timing events (phase timer)
   }
+  // the graph executables go first; the streams and events they were captured from release themselves
   ~MnistEngine() override {
     for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
-    hipEventDestroy(ev_a_);
-    hipEventDestroy(ev_b_);
-    hipEventDestroy(ev_done_);
-    hipStreamDestroy(comm_stream_);
-    hipStreamDestroy(opt_stream_);
-    hipEventDestroy(ev_opt_a_);
-    hipEventDestroy(ev_start_);
-    hipEventDestroy(ev_ag_);
-    hipEventDestroy(ev_p2_);
-    hipEventDestroy(ev_wag_);
-    for (auto& e : pev_) hipEventDestroy(e);
   }
 
   // ---- state accessors (views share storage with the engine) ----
@@ -343,21 +323,10 @@ class MnistEngine : public torch::CustomClassHolder {
   // Optimizer over the flat range [beg, end) on stream s; t = global_step + t_offset.
   void apply_optimizer_range(int64_t beg, int64_t end, double grad_scale, int t_offset, hipStream_t s,
                              const int64_t* tsrc = nullptr) {
-    const uint16_t* gbf = (bf16_comm_ && dp()) ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr;
-    const int64_t n = end - beg;
-    if (opt_ == 0) {
-      AdamArgs a{(float*)params_.data_ptr() + beg, (float*)m_.data_ptr() + beg, (float*)v_.data_ptr() + beg,
-                 (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, sched_,
-                 (float)b1_, (float)b2_, (float)eps_, tsrc ? tsrc : (const int64_t*)step_.data_ptr(), t_offset,
-                 (float)grad_scale};
-      adam_apply(a, s);
-    } else {
-      SgdArgs a{(float*)params_.data_ptr() + beg, opt_ == 2 ? (float*)m_.data_ptr() + beg : nullptr,
-                (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg, gbf, n, sched_,
-                (float)momentum_, 0.f, (float)grad_scale, nesterov_ ? 1 : 0,
-                tsrc ? tsrc : (const int64_t*)step_.data_ptr(), t_offset};
-      sgd_apply(a, s);
-    }
+    if (!tsrc) tsrc = (const int64_t*)step_.data_ptr();
+    const bool bf_grads = bf16_comm_ && dp();
+    if (opt_ == 0) adam_apply(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
+    else sgd_apply(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
   }
 
   // Full synchronous data-parallel step (the reference's SyncReplicasOptimizer global step with
@@ -367,6 +336,9 @@ class MnistEngine : public torch::CustomClassHolder {
   void train_step() { train_step_impl(true); }
 
   void train_step_impl(bool join_end) {
+    // checked before anything is launched: the sharded schedules read the bf16 shadow, which the
+    // fp32 step leaves stale
+    TORCH_CHECK(!(zero_ && fp32_), "ZeRO-1 is a bf16-path option: set_zero(False) or set_dtype('bf16')");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -393,14 +365,11 @@ class MnistEngine : public torch::CustomClassHolder {
     // weight-gradient slabs itself and bumps the step (its t was written by the head kernel).
     const bool fused = opt_ == 0 && fuse_tail_;
     if (fused) a.t_out = (int64_t*)tnext_.data_ptr();
-    MnistAdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
-                    (uint16_t*)pbf_.data_ptr(), sched_, (float)b1_, (float)b2_, (float)eps_,
-                    (const int64_t*)tnext_.data_ptr(), (int64_t*)step_.data_ptr(), nullptr};
     // bf16 fc-region gradients (the DP wire format): the fc backward writes 2 B and Adam reads
     // 2 B per gradient instead of 4 + 4 (13 MB less HBM traffic per step)
     const bool gbf_local = fused && local_bf16_grads_;
     if (gbf_local) a.gbf_a = (uint16_t*)gbf_.data_ptr();
-    o.gbf = gbf_local ? (const uint16_t*)gbf_.data_ptr() : nullptr;
+    const MnistAdamArgs o = fused_adam_args((uint16_t*)pbf_.data_ptr(), gbf_local);
     mnist_forward_conv(a, s);
     tag("conv_fwd", s);
     mnist_forward_fc(a, true, s);
@@ -442,12 +411,7 @@ class MnistEngine : public torch::CustomClassHolder {
     const double scale = 1.0 / (double)world();
     const bool bf = bf16_comm_;
     MnistStepArgs a = args();
-    a.t_out = (int64_t*)tnext_.data_ptr();
-    a.step_bump = (int64_t*)step_.data_ptr();
-    if (bf) {
-      a.gbf_a = (uint16_t*)gbf_.data_ptr();
-      a.gbf_b = (uint16_t*)gbf_.data_ptr();
-    }
+    set_dp_outputs(a, bf);
     mark(P_START, s);
     mnist_forward_conv(a, s);
     tag("conv_fwd", s);
@@ -461,14 +425,12 @@ class MnistEngine : public torch::CustomClassHolder {
     mnist_backward_a(a, s, 0);
     tag("fc_bwd", s);
     mark(P_BFC, s);
-    HIP_OK(hipEventRecord(ev_a_, s));
-    wait(comm_stream_, ev_a_, "ar_fc<-fc_bwd");
+    hand_off(s, ev_a_, comm_stream_, "ar_fc<-fc_bwd");
     mark(P_CA0, comm_stream_);
     reduce_bucket(BUCKET_SPLIT, TOTAL, bf);
     tag("ar_fc", comm_stream_);
     mark(P_CA1, comm_stream_);
-    HIP_OK(hipEventRecord(ev_ag_, comm_stream_));
-    wait(opt_stream_, ev_ag_, "opt_fc<-ar_fc");
+    hand_off(comm_stream_, ev_ag_, opt_stream_, "opt_fc<-ar_fc");
     apply_optimizer_range(BUCKET_SPLIT, TOTAL, scale, 0, opt_stream_, (const int64_t*)tnext_.data_ptr());
     tag("opt_fc", opt_stream_);
     HIP_OK(hipEventRecord(ev_opt_a_, opt_stream_));
@@ -476,14 +438,7 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("conv_bwd", s);
     mnist_conv_grad_reduce(a, s);
     tag("slab_reduce", s);
-    mark(P_BCONV, s);
-    HIP_OK(hipEventRecord(ev_b_, s));
-    wait(comm_stream_, ev_b_, "ar_conv<-slab_reduce");
-    mark(P_CB0, comm_stream_);
-    reduce_bucket(0, BUCKET_SPLIT, bf);
-    tag("ar_conv", comm_stream_);
-    mark(P_CB1, comm_stream_);
-    HIP_OK(hipEventRecord(ev_done_, comm_stream_));
+    all_reduce_conv(s, bf);
     wait(s, ev_done_, "opt_conv<-ar_conv");
     apply_optimizer_range(0, BUCKET_SPLIT, scale, 0, s);
     tag("opt_conv", s);
@@ -515,24 +470,13 @@ class MnistEngine : public torch::CustomClassHolder {
       const int64_t rows = zshard_ / HID;
       mnist_sfb_tile_rows((int)(rk * rows), (int)((rk + 1) * rows), &a.sfb_by_lo, &a.sfb_by_hi);
     }
-    a.t_out = (int64_t*)tnext_.data_ptr();
-    a.step_bump = (int64_t*)step_.data_ptr();
-    if (bf) {
-      a.gbf_a = (uint16_t*)gbf_.data_ptr();
-      a.gbf_b = (uint16_t*)gbf_.data_ptr();
-    }
+    set_dp_outputs(a, bf);
     mark(P_START, s);
-    if (shard && pending_wag_ && !wag_issued_) {  // last step's fc1 bf16 shards -> every rank, beside the conv fwd
-      HIP_OK(hipEventRecord(ev_start_, s));
-      wait(comm_stream_, ev_start_, "wag<-opt");
-      ag_w(comm_stream_);
-      tag("wag", comm_stream_);
-      HIP_OK(hipEventRecord(ev_wag_, comm_stream_));
-    }
+    // last step's fc1 bf16 shards -> every rank, beside the conv fwd
+    if (shard && pending_wag_ && !wag_issued_) gather_weights(s, "wag<-opt");
     mnist_forward_conv(a, s);
     tag("conv_fwd", s);
-    HIP_OK(hipEventRecord(ev_p2_, s));
-    wait(comm_stream_, ev_p2_, "gather_p2<-conv_fwd");
+    hand_off(s, ev_p2_, comm_stream_, "gather_p2<-conv_fwd");
     mark(P_CA0, comm_stream_);
     gather_sfb(true, comm_stream_);
     tag("gather_p2", comm_stream_);
@@ -543,8 +487,7 @@ class MnistEngine : public torch::CustomClassHolder {
     mnist_forward_fc(a, true, s);
     tag("fc_fwd", s);
     mark(P_FWD, s);
-    HIP_OK(hipEventRecord(ev_a_, s));
-    wait(comm_stream_, ev_a_, "gather_dr<-fc_fwd");
+    hand_off(s, ev_a_, comm_stream_, "gather_dr<-fc_fwd");
     gather_sfb(false, comm_stream_);
     tag("gather_dr", comm_stream_);
     mark(P_CA1, comm_stream_);
@@ -554,16 +497,6 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_BFC, s);
     mnist_backward_b(a, s);
     tag("conv_bwd", s);
-    auto ar_conv = [&]() {
-      mark(P_BCONV, s);
-      HIP_OK(hipEventRecord(ev_b_, s));
-      wait(comm_stream_, ev_b_, "ar_conv<-slab_reduce");
-      mark(P_CB0, comm_stream_);
-      reduce_bucket(0, BUCKET_SPLIT, bf);
-      tag("ar_conv", comm_stream_);
-      mark(P_CB1, comm_stream_);
-      HIP_OK(hipEventRecord(ev_done_, comm_stream_));
-    };
     if (merge_tail_) {
       // ONE launch for the slab reduce and the SFB GEMM (their blocks side by side); the conv
       // bucket's all-reduce then runs beside the fc-region optimizer instead of beside the GEMM
@@ -571,11 +504,11 @@ class MnistEngine : public torch::CustomClassHolder {
       mnist_fc_grad_sfb(a, s, true);
       tag("sfb_gemm", s);
       tag_alias("slab_reduce");
-      ar_conv();
+      all_reduce_conv(s, bf);
     } else {
       mnist_conv_grad_reduce(a, s);
       tag("slab_reduce", s);
-      ar_conv();
+      all_reduce_conv(s, bf);
       wait(s, ev_ag_, "sfb_gemm<-gather_dr");
       mnist_fc_grad_sfb(a, s);  // beside the conv bucket's all-reduce
       tag("sfb_gemm", s);
@@ -592,20 +525,13 @@ class MnistEngine : public torch::CustomClassHolder {
       const int64_t end[3] = {BUCKET_SPLIT, OFF_WD1 + (rk + 1) * zshard_, TOTAL};
       if (opt_ == 0 && BUCKET_SPLIT % 4 == 0 && zshard_ % 4 == 0) {  // one launch over the ranges
         const int64_t n[3] = {end[0] - beg[0], end[1] - beg[1], end[2] - beg[2]};
-        AdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
-                   (const float*)grad_.data_ptr(), (uint16_t*)pbf_.data_ptr(),
-                   bf16_comm_ ? (const uint16_t*)gbf_.data_ptr() : nullptr, 0, sched_, (float)b1_, (float)b2_,
-                   (float)eps_, t, 0, (float)scale};
+        const AdamArgs o = adam_args(0, 0, bf16_comm_, scale, 0, t);  // buffer bases; n comes per range
         if (split_opt) {
           adam_apply_ranges(o, 2, beg + 1, n + 1, s);
           tag("opt_fc", s);
           // the updated shard can leave now: the gather queues behind the conv bucket's all-reduce on
           // the comm stream and runs beside the conv-region Adam and the next conv forward
-          HIP_OK(hipEventRecord(ev_start_, s));
-          wait(comm_stream_, ev_start_, "wag<-opt_fc");
-          ag_w(comm_stream_);
-          tag("wag", comm_stream_);
-          HIP_OK(hipEventRecord(ev_wag_, comm_stream_));
+          gather_weights(s, "wag<-opt_fc");
           wag_issued_ = true;
           wait(s, ev_done_, "opt_conv<-ar_conv");
           adam_apply_ranges(o, 1, beg, n, s);
@@ -623,13 +549,7 @@ class MnistEngine : public torch::CustomClassHolder {
       }
       pending_wag_ = true;
       if (join_end) {  // the caller reads whole weights after this step: gather the shards now
-        if (!wag_issued_) {
-          HIP_OK(hipEventRecord(ev_start_, s));
-          wait(comm_stream_, ev_start_, "wag<-opt");
-          ag_w(comm_stream_);
-          tag("wag", comm_stream_);
-          HIP_OK(hipEventRecord(ev_wag_, comm_stream_));
-        }
+        if (!wag_issued_) gather_weights(s, "wag<-opt");
         wait(s, ev_wag_, "end<-wag");
         pending_wag_ = wag_issued_ = false;
       }
@@ -649,7 +569,6 @@ class MnistEngine : public torch::CustomClassHolder {
   // fp32 step: forward, backward (fc grads + conv slabs), slab reduce + step bump, [fp32
   // all-reduce of the whole buffer], optimizer (t = bumped step).
   void train_step_f32(bool dp) {
-    TORCH_CHECK(!zero_, "ZeRO-1 is a bf16-path option");
     hipStream_t s = stream();
     MnistF32Args f = args_f32();
     // one GPU + Adam: ONE tail kernel reduces the conv slabs, runs Adam over every region and bumps
@@ -668,11 +587,8 @@ class MnistEngine : public torch::CustomClassHolder {
     if (fused) {
       // no bf16 shadow: nothing in fp32 mode reads it (set_dtype("bf16") re-derives it), and its
       // 6.5 MB of writes are 1 us of the bandwidth-bound optimizer tail
-      MnistAdamArgs o{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(),
-                      nullptr, sched_, (float)b1_, (float)b2_, (float)eps_,
-                      (const int64_t*)tnext_.data_ptr(), (int64_t*)step_.data_ptr(), nullptr};
       mark(P_BCONV, s);
-      mnist_adam_fused(r, o, s, true);
+      mnist_adam_fused(r, fused_adam_args(nullptr, false), s, true);
       mark(P_OPT, s);
       return;
     }
@@ -680,15 +596,13 @@ class MnistEngine : public torch::CustomClassHolder {
     mnist_conv_grad_reduce(r, s);
     mark(P_BCONV, s);
     if (dp) {
-      HIP_OK(hipEventRecord(ev_b_, s));
-      HIP_OK(hipStreamWaitEvent(comm_stream_, ev_b_, 0));
+      hand_off(s, ev_b_, comm_stream_, "f32:ar<-slab_reduce");
       mark(P_CA0, comm_stream_);
       reduce_bucket(0, TOTAL, false);
       mark(P_CA1, comm_stream_);
       mark(P_CB0, comm_stream_);
       mark(P_CB1, comm_stream_);
-      HIP_OK(hipEventRecord(ev_done_, comm_stream_));
-      HIP_OK(hipStreamWaitEvent(s, ev_done_, 0));
+      hand_off(comm_stream_, ev_done_, s, "f32:opt<-ar");
     }
     apply_optimizer_range(0, TOTAL, 1.0 / (double)world(), 0, s);
     mark(P_OPT, s);
@@ -701,12 +615,11 @@ class MnistEngine : public torch::CustomClassHolder {
     const int64_t r = rank_in_comm();
     MnistStepArgs a = args();
     // all-gather last step's updated fc1 shadow shards, overlapping the conv forward
-    HIP_OK(hipEventRecord(ev_start_, s));
-    HIP_OK(hipStreamWaitEvent(comm_stream_, ev_start_, 0));
+    hand_off(s, ev_start_, comm_stream_, "zero:wag<-prev_opt");
     ag_w(comm_stream_);
     HIP_OK(hipEventRecord(ev_ag_, comm_stream_));
     mnist_forward_conv(a, s);
-    HIP_OK(hipStreamWaitEvent(s, ev_ag_, 0));
+    wait(s, ev_ag_, "zero:fc_fwd<-wag");
     mnist_forward_fc(a, true, s);
     // bf16 wire format for both buckets, produced by the kernels themselves -- the same rounding
     // points as train_step_dp (the conv bucket used to be summed from fp32 and rounded after the
@@ -717,8 +630,7 @@ class MnistEngine : public torch::CustomClassHolder {
       a.gbf_b = (uint16_t*)gbf_.data_ptr();
     }
     mnist_backward_a(a, s);
-    HIP_OK(hipEventRecord(ev_a_, s));
-    HIP_OK(hipStreamWaitEvent(comm_stream_, ev_a_, 0));
+    hand_off(s, ev_a_, comm_stream_, "zero:rs_fc<-fc_bwd");
     rs_w(comm_stream_);
     reduce_bucket(OFF_BD1, TOTAL, in_gbf(OFF_BD1));
     apply_optimizer_range(OFF_WD1 + r * zshard_, OFF_WD1 + (r + 1) * zshard_, scale, 1, comm_stream_);
@@ -726,13 +638,11 @@ class MnistEngine : public torch::CustomClassHolder {
     HIP_OK(hipEventRecord(ev_opt_a_, comm_stream_));
     a.step_bump = (int64_t*)step_.data_ptr();
     mnist_backward_b(a, s);
-    HIP_OK(hipStreamWaitEvent(s, ev_opt_a_, 0));
+    wait(s, ev_opt_a_, "zero:slab_reduce<-opt_fc");
     mnist_conv_grad_reduce(a, s);
-    HIP_OK(hipEventRecord(ev_b_, s));
-    HIP_OK(hipStreamWaitEvent(comm_stream_, ev_b_, 0));
+    hand_off(s, ev_b_, comm_stream_, "zero:ar_conv<-slab_reduce");
     reduce_bucket(0, BUCKET_SPLIT, pre_b);
-    HIP_OK(hipEventRecord(ev_done_, comm_stream_));
-    HIP_OK(hipStreamWaitEvent(s, ev_done_, 0));
+    hand_off(comm_stream_, ev_done_, s, "zero:opt_conv<-ar_conv");
     apply_optimizer_range(0, BUCKET_SPLIT, scale, 0, s);
   }
 
@@ -743,11 +653,9 @@ class MnistEngine : public torch::CustomClassHolder {
     hipStream_t s = stream();
     if (weight != 1.0) scale_f32((float*)grad_.data_ptr(), TOTAL, (float)weight, s);
     if (!dp()) return;
-    HIP_OK(hipEventRecord(ev_a_, s));
-    HIP_OK(hipStreamWaitEvent(comm_stream_, ev_a_, 0));
+    hand_off(s, ev_a_, comm_stream_, "reduce_grads:ar<-grads");
     reduce_bucket(0, TOTAL, false);
-    HIP_OK(hipEventRecord(ev_done_, comm_stream_));
-    HIP_OK(hipStreamWaitEvent(s, ev_done_, 0));
+    hand_off(comm_stream_, ev_done_, s, "reduce_grads:end<-ar");
   }
 
   // Evaluate on an explicit batch (x [n,784] fp32, y [n] int32) in chunks of <= B.
@@ -789,50 +697,24 @@ class MnistEngine : public torch::CustomClassHolder {
   // n steps removes the host launch and the graph-to-graph boundary from n - 1 of them.
   void capture_train_steps(const std::string& name, int64_t n) {
     TORCH_CHECK(n >= 1 && n <= 1000, "capture_train_steps: 1 <= n <= 1000");
-    hipStream_t s = stream();
-    TORCH_CHECK(s != nullptr, "capture needs a non-default stream (use torch.cuda.stream(...))");
+    hipStream_t s = capture_stream();
     drop_graph(name);
-    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-    try {
-      for (int64_t i = 0; i < n; ++i) train_step_impl(i == n - 1);
-    } catch (...) {
-      hipGraph_t g;
-      hipStreamEndCapture(s, &g);
-      if (g) hipGraphDestroy(g);
-      throw;
-    }
-    hipGraph_t g = nullptr;
-    HIP_OK(hipStreamEndCapture(s, &g));
-    hipGraphExec_t ex = nullptr;
-    HIP_OK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
-    HIP_OK(hipGraphDestroy(g));
-    graphs_[name] = ex;
+    StreamCapture cap(s);
+    for (int64_t i = 0; i < n; ++i) train_step_impl(i == n - 1);
+    store_graph(name, cap);
   }
   // forward + backward (fc gradients, conv slab reduce, step bump) as one graph, no optimizer: the
   // compute part of a parameter-server worker step (the update runs on the PS task's GPU,
   // csrc/runtime/gpu_ps.cpp). Replayed with replay(name, 1) after the batch is fed.
   void capture_grads(const std::string& name) {
-    hipStream_t s = stream();
-    TORCH_CHECK(s != nullptr, "capture needs a non-default stream (use torch.cuda.stream(...))");
+    hipStream_t s = capture_stream();
     drop_graph(name);
     timed_ = false;
-    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-    try {
-      forward(true);
-      backward_a();
-      backward_b();
-    } catch (...) {
-      hipGraph_t g;
-      hipStreamEndCapture(s, &g);
-      if (g) hipGraphDestroy(g);
-      throw;
-    }
-    hipGraph_t g = nullptr;
-    HIP_OK(hipStreamEndCapture(s, &g));
-    hipGraphExec_t ex = nullptr;
-    HIP_OK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
-    HIP_OK(hipGraphDestroy(g));
-    graphs_[name] = ex;
+    StreamCapture cap(s);
+    forward(true);
+    backward_a();
+    backward_b();
+    store_graph(name, cap);
   }
   void replay(const std::string& name, int64_t times) {
     auto it = graphs_.find(name);
@@ -857,58 +739,46 @@ class MnistEngine : public torch::CustomClassHolder {
   // operand and that its consumers depend on it (read-after-write and write-after-read across steps).
   std::vector<std::string> capture_topology(int64_t n) {
     TORCH_CHECK(n >= 1 && n <= 8, "capture_topology: 1 <= n <= 8");
-    hipStream_t s = stream();
-    TORCH_CHECK(s != nullptr, "capture needs a non-default stream (use torch.cuda.stream(...))");
     topo_seen_.clear();
     topo_tags_.clear();
-    topo_ = true;
-    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+    StreamCapture cap(capture_stream());
     try {
+      topo_ = true;
       for (int64_t i = 0; i < n; ++i) {
         topo_step_ = i;
         train_step_impl(i == n - 1);
       }
+      topo_ = false;
     } catch (...) {
       topo_ = false;
-      hipGraph_t g = nullptr;
-      hipStreamEndCapture(s, &g);
-      if (g) hipGraphDestroy(g);
       throw;
     }
-    topo_ = false;
-    hipGraph_t g = nullptr;
-    HIP_OK(hipStreamEndCapture(s, &g));
+    hipGraph_t g = cap.end();
     std::vector<std::string> out;
-    try {
-      size_t nn = 0, ne = 0;
-      HIP_OK(hipGraphGetNodes(g, nullptr, &nn));
-      std::vector<hipGraphNode_t> nodes(nn);
-      HIP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
-      std::map<hipGraphNode_t, size_t> idx;
-      for (size_t i = 0; i < nn; ++i) {
-        idx[nodes[i]] = i;
-        hipGraphNodeType ty = hipGraphNodeTypeEmpty;
-        HIP_OK(hipGraphNodeGetType(nodes[i], &ty));
-        out.push_back("node " + std::to_string(i) + " " + std::to_string((int)ty));
-      }
-      HIP_OK(hipGraphGetEdges(g, nullptr, nullptr, &ne));
-      std::vector<hipGraphNode_t> from(ne), to(ne);
-      if (ne) HIP_OK(hipGraphGetEdges(g, from.data(), to.data(), &ne));
-      for (size_t e = 0; e < ne; ++e)
-        out.push_back("edge " + std::to_string(idx.at(from[e])) + " " + std::to_string(idx.at(to[e])));
-      for (auto& kv : topo_tags_) {
-        std::string line = "tag " + kv.first;
-        for (auto nd : kv.second) {
-          auto it = idx.find(nd);
-          if (it != idx.end()) line += " " + std::to_string(it->second);
-        }
-        out.push_back(line);
-      }
-    } catch (...) {
-      hipGraphDestroy(g);
-      throw;
+    size_t nn = 0, ne = 0;
+    HIP_OK(hipGraphGetNodes(g, nullptr, &nn));
+    std::vector<hipGraphNode_t> nodes(nn);
+    HIP_OK(hipGraphGetNodes(g, nodes.data(), &nn));
+    std::map<hipGraphNode_t, size_t> idx;
+    for (size_t i = 0; i < nn; ++i) {
+      idx[nodes[i]] = i;
+      hipGraphNodeType ty = hipGraphNodeTypeEmpty;
+      HIP_OK(hipGraphNodeGetType(nodes[i], &ty));
+      out.push_back("node " + std::to_string(i) + " " + std::to_string((int)ty));
     }
-    HIP_OK(hipGraphDestroy(g));
+    HIP_OK(hipGraphGetEdges(g, nullptr, nullptr, &ne));
+    std::vector<hipGraphNode_t> from(ne), to(ne);
+    if (ne) HIP_OK(hipGraphGetEdges(g, from.data(), to.data(), &ne));
+    for (size_t e = 0; e < ne; ++e)
+      out.push_back("edge " + std::to_string(idx.at(from[e])) + " " + std::to_string(idx.at(to[e])));
+    for (auto& kv : topo_tags_) {
+      std::string line = "tag " + kv.first;
+      for (auto nd : kv.second) {
+        auto it = idx.find(nd);
+        if (it != idx.end()) line += " " + std::to_string(it->second);
+      }
+      out.push_back(line);
+    }
     topo_tags_.clear();
     topo_seen_.clear();
     return out;
@@ -940,17 +810,13 @@ class MnistEngine : public torch::CustomClassHolder {
     a.sfb_dr = (const uint16_t*)dr.data_ptr();
     a.sfb_rs = rs;
     mnist_fc_grad_sfb(a, s);  // warm (kernel attributes)
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0));
-    HIP_OK(hipEventCreate(&e1));
+    HipEvent e0(true), e1(true);
     HIP_OK(hipEventRecord(e0, s));
     for (int64_t i = 0; i < iters; ++i) mnist_fc_grad_sfb(a, s);
     HIP_OK(hipEventRecord(e1, s));
     HIP_OK(hipEventSynchronize(e1));
     float ms = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     return (double)ms / (double)iters;
   }
 
@@ -960,20 +826,87 @@ class MnistEngine : public torch::CustomClassHolder {
   void mark(int k, hipStream_t st) {
     if (timing_) HIP_OK(hipEventRecord(pev_[k], st));
   }
+  // The stream a capture runs on. StreamCapture (hip_util.h) issues the hipStreamBeginCapture.
+  hipStream_t capture_stream() {
+    hipStream_t s = stream();
+    TORCH_CHECK(s != nullptr, "capture needs a non-default stream (use torch.cuda.stream(...))");
+    return s;
+  }
+  // ends the capture and keeps its instantiated graph under `name` for replay()
+  void store_graph(const std::string& name, StreamCapture& cap) {
+    hipGraphExec_t ex = nullptr;
+    HIP_OK(hipGraphInstantiate(&ex, cap.end(), nullptr, nullptr, 0));
+    graphs_[name] = ex;
+  }
   // A cross-stream dependency of the schedule: `st` waits for `ev`. `name` ("consumer<-producer")
-  // identifies the edge for the topology test's fault injection (set_debug_drop_wait).
+  // identifies the edge for the topology test's fault injection (set_debug_drop_wait). Every wait of
+  // the engine goes through here.
   void wait(hipStream_t st, hipEvent_t ev, const char* name) {
     if (!drop_wait_.empty() && drop_wait_ == name) return;
     HIP_OK(hipStreamWaitEvent(st, ev, 0));
   }
-  // capture_topology: the graph nodes this operation added (everything new since the last tag; the
-  // host issues operations one after another, so the difference is exactly this operation's nodes)
+  // `to` goes on only after everything queued on `from` so far: record `ev` there, wait for it here
+  void hand_off(hipStream_t from, hipEvent_t ev, hipStream_t to, const char* name) {
+    HIP_OK(hipEventRecord(ev, from));
+    wait(to, ev, name);
+  }
+  // ZeRO + SFB: the updated fc1 bf16 shards go to every rank on the comm stream, behind what `s` has
+  // queued so far (`name` names that wait). The consumer waits for ev_wag_ later, where it needs them.
+  void gather_weights(hipStream_t s, const char* name) {
+    hand_off(s, ev_start_, comm_stream_, name);
+    ag_w(comm_stream_);
+    tag("wag", comm_stream_);
+    HIP_OK(hipEventRecord(ev_wag_, comm_stream_));
+  }
+  // bf16 DP steps: the conv bucket's all-reduce on the comm stream, behind the slab reduce on `s`.
+  // The consumer waits for ev_done_ later, where it needs the reduced bucket.
+  void all_reduce_conv(hipStream_t s, bool pre) {
+    mark(P_BCONV, s);
+    hand_off(s, ev_b_, comm_stream_, "ar_conv<-slab_reduce");
+    mark(P_CB0, comm_stream_);
+    reduce_bucket(0, BUCKET_SPLIT, pre);
+    tag("ar_conv", comm_stream_);
+    mark(P_CB1, comm_stream_);
+    HIP_OK(hipEventRecord(ev_done_, comm_stream_));
+  }
+
+  // ---- argument structs of the optimizer kernels: each is filled in one place ----
+  // Range [beg, beg + n) of the flat buffers; bf_grads: the gradients are bf16 in gbf_
+  AdamArgs adam_args(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t) {
+    return AdamArgs{(float*)params_.data_ptr() + beg, (float*)m_.data_ptr() + beg, (float*)v_.data_ptr() + beg,
+                    (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg,
+                    bf_grads ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr, n, sched_, (float)b1_,
+                    (float)b2_, (float)eps_, t, t_offset, (float)grad_scale};
+  }
+  SgdArgs sgd_args(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t) {
+    return SgdArgs{(float*)params_.data_ptr() + beg, opt_ == 2 ? (float*)m_.data_ptr() + beg : nullptr,
+                   (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg,
+                   bf_grads ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr, n, sched_, (float)momentum_, 0.f,
+                   (float)grad_scale, nesterov_ ? 1 : 0, t, t_offset};
+  }
+  // one-GPU fused tail (slab reduce + Adam over every region + step bump). pbf: the bf16 shadow to
+  // write, null for none; bf_grads: the fc-region gradients are bf16 in gbf_
+  MnistAdamArgs fused_adam_args(uint16_t* pbf, bool bf_grads) {
+    return MnistAdamArgs{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(), pbf, sched_,
+                         (float)b1_, (float)b2_, (float)eps_, (const int64_t*)tnext_.data_ptr(),
+                         (int64_t*)step_.data_ptr(), bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr};
+  }
+  // bf16 DP steps: the head kernel writes the optimizer's t, the slab reduce bumps the step, and with
+  // a bf16 wire format (bf) both buckets' gradients come out of the kernels as bf16 in gbf_
+  void set_dp_outputs(MnistStepArgs& a, bool bf) {
+    a.t_out = (int64_t*)tnext_.data_ptr();
+    a.step_bump = (int64_t*)step_.data_ptr();
+    if (bf) a.gbf_a = a.gbf_b = (uint16_t*)gbf_.data_ptr();
+  }
+
   // capture_topology: the last operation's nodes under a second label (one launch doing two jobs)
   void tag_alias(const char* label) {
     if (!topo_ || topo_tags_.empty()) return;
     auto nodes = topo_tags_.back().second;
     topo_tags_.emplace_back(std::string(label) + "@" + std::to_string(topo_step_), std::move(nodes));
   }
+  // capture_topology: the graph nodes this operation added (everything new since the last tag; the
+  // host issues operations one after another, so the difference is exactly this operation's nodes)
   void tag(const char* label, hipStream_t st) {
     if (!topo_) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1007,51 +940,18 @@ class MnistEngine : public torch::CustomClassHolder {
 
   // ZeRO helpers (fc1 weight region W = [OFF_WD1, OFF_BD1))
   void rs_w(hipStream_t st) {
-    const int64_t r = rank_in_comm();
-    const int64_t S = zshard_;
-    const bool pre = in_gbf(OFF_WD1);
-    if (comm_) {
-      if (bf16_comm_) {
-        uint16_t* gb = (uint16_t*)gbf_.data_ptr() + OFF_WD1;
-        if (!pre) cast_f32_bf16((const float*)grad_.data_ptr() + OFF_WD1, gb, OFF_BD1 - OFF_WD1, st);
-        comm_->reduce_scatter_raw(gb, gb + r * S, (size_t)S, ncclBfloat16, ncclSum, st);
-      } else {
-        float* g = (float*)grad_.data_ptr() + OFF_WD1;
-        comm_->reduce_scatter_raw(g, g + r * S, (size_t)S, ncclFloat32, ncclSum, st);
-      }
-    } else {
-      void* out = bf16_comm_ ? (void*)((uint16_t*)gbf_.data_ptr() + OFF_WD1 + r * S)
-                             : (void*)((float*)grad_.data_ptr() + OFF_WD1 + r * S);
-      const void* in = pre ? (const void*)((const uint16_t*)gbf_.data_ptr() + OFF_WD1)
-                           : (const void*)((const float*)grad_.data_ptr() + OFF_WD1);
-      ipc_->reduce_scatter_raw(in, pre, out, bf16_comm_, S, 1.0, st);
-    }
+    reduce_scatter_grads(OFF_WD1, zshard_, in_gbf(OFF_WD1), st);
   }
-  // The updated bf16 fc1 shards -> every rank. Through the IPC one-shot all-gather (every rank reads
-  // all peers' shards at once over all xGMI links) when its staging holds a shard -- at 8 ranks the
-  // 0.8 MB shard exactly fills the staging sized for the SFB p2 gather -- else RCCL's all-gather.
+  // The updated bf16 fc1 shards -> every rank. At 8 ranks the 0.8 MB shard exactly fills the IPC
+  // staging sized for the SFB p2 gather.
   void ag_w(hipStream_t st) {
-    const int64_t r = rank_in_comm();
-    const int64_t S = zshard_;
-    uint16_t* pb = (uint16_t*)pbf_.data_ptr() + OFF_WD1;
-    if (ipc_gathers(S)) ipc_->all_gather_raw(pb, 2, S, st);
-    else if (comm_) comm_->all_gather_raw(pb + r * S, pb, (size_t)S, ncclBfloat16, st);
-    else TORCH_CHECK(false, "ZeRO weight gather: no communicator holds a ", S, "-element shard");
+    all_gather_bf16((uint16_t*)pbf_.data_ptr() + OFF_WD1, zshard_, st, "ZeRO weight gather");
   }
 
   bool sfb_active() const { return sfb_ && !fp32_ && dp() && sfp2_.defined(); }
-  // in-place all-gather of one SFB factor array ([W][S], this rank's shard at r*S): IPC when its
-  // staging holds the shard (one kernel reading every peer at once), else RCCL
+  // in-place all-gather of one SFB factor array ([W][S], this rank's shard at r*S)
   void gather_sfb(bool p2part, hipStream_t st) {
-    const int64_t r = rank_in_comm();
-    uint16_t* base = (uint16_t*)(p2part ? sfp2_ : sfdr_).data_ptr();
-    const int64_t S = p2part ? B_ * FEAT : sfb_rs_;
-    if (ipc_gathers(S)) {
-      ipc_->all_gather_raw(base, 2, S, st);
-      return;
-    }
-    TORCH_CHECK(comm_, "SFB gather: no communicator holds a ", S, "-element shard");
-    comm_->all_gather_raw(base + r * S, base, (size_t)S, ncclBfloat16, st);
+    all_gather_bf16((uint16_t*)(p2part ? sfp2_ : sfdr_).data_ptr(), p2part ? B_ * FEAT : sfb_rs_, st, "SFB gather");
   }
 
   // bucket A's gradients come out of the fc backward as bf16 in gbf_ (MnistStepArgs::gbf_a)
@@ -1059,24 +959,52 @@ class MnistEngine : public torch::CustomClassHolder {
   bool in_gbf(int64_t beg) const { return fused_bf16_a() && beg >= BUCKET_SPLIT; }
 
   // pre: the bucket's gradients are already bf16 in gbf_ (written by the producing kernel)
-  void reduce_bucket(int64_t beg, int64_t end, bool pre) {
-    const size_t n = (size_t)(end - beg);
-    if (ipc_ && (!comm_ || (int64_t)n <= ipc_small_)) {
-      // fp32 (or fused bf16) grads in, fp32 sum in rank order, written where the optimizer reads
-      // (bf16 gbf or fp32 grad)
-      void* out = bf16_comm_ ? (void*)((uint16_t*)gbf_.data_ptr() + beg) : (void*)((float*)grad_.data_ptr() + beg);
-      const void* in = pre ? (const void*)((const uint16_t*)gbf_.data_ptr() + beg)
-                           : (const void*)((const float*)grad_.data_ptr() + beg);
-      ipc_->all_reduce_raw(in, pre, out, bf16_comm_, (int64_t)n, 1.0, comm_stream_);
+  void reduce_bucket(int64_t beg, int64_t end, bool pre) { all_reduce_grads(beg, end - beg, pre, comm_stream_); }
+
+  // ---- collectives: the one place each chooses between the IPC and the RCCL transport ----
+  // In-place all-gather of a bf16 array [W][S] with this rank's shard at r*S: the IPC one-shot gather
+  // (one kernel reading every peer at once over all xGMI links) when its staging holds a shard, else
+  // RCCL's. sync_params' fp32 gathers prefer RCCL and keep their own code.
+  void all_gather_bf16(uint16_t* base, int64_t S, hipStream_t st, const char* what) {
+    if (ipc_gathers(S)) ipc_->all_gather_raw(base, 2, S, st);
+    else if (comm_) comm_->all_gather_raw(base + rank_in_comm() * S, base, (size_t)S, ncclBfloat16, st);
+    else TORCH_CHECK(false, what, ": no communicator holds a ", S, "-element shard");
+  }
+  // Operands of a gradient collective on the flat range starting at beg. IPC reads the gradients
+  // where the kernels wrote them (pre: as bf16 in gbf_, else fp32 in grad_), sums in fp32 in rank
+  // order and writes where the optimizer reads: the wire format, bf16 in gbf_ or fp32 in grad_.
+  // RCCL reduces in place in the wire format, so fp32 gradients are cast to it first.
+  const void* grad_src(int64_t beg, bool pre) const {
+    if (pre) return (const uint16_t*)gbf_.data_ptr() + beg;
+    return (const float*)grad_.data_ptr() + beg;
+  }
+  void* grad_wire(int64_t beg) const {
+    if (bf16_comm_) return (uint16_t*)gbf_.data_ptr() + beg;
+    return (float*)grad_.data_ptr() + beg;
+  }
+  void* rccl_wire(int64_t beg, int64_t n, bool pre, hipStream_t st) {
+    if (bf16_comm_ && !pre) cast_f32_bf16((const float*)grad_.data_ptr() + beg, (uint16_t*)grad_wire(beg), n, st);
+    return grad_wire(beg);
+  }
+  ncclDataType_t wire_type() const { return bf16_comm_ ? ncclBfloat16 : ncclFloat32; }
+  // Sum all-reduce of n gradients at beg: IPC without RCCL or for a latency-bound bucket
+  // (<= ipc_small_ elements), else RCCL
+  void all_reduce_grads(int64_t beg, int64_t n, bool pre, hipStream_t st) {
+    if (ipc_ && (!comm_ || n <= ipc_small_)) {
+      ipc_->all_reduce_raw(grad_src(beg, pre), pre, grad_wire(beg), bf16_comm_, n, 1.0, st);
       return;
     }
     TORCH_CHECK(comm_, "no communicator for a ", n, "-element bucket");
-    if (bf16_comm_) {
-      uint16_t* gb = (uint16_t*)gbf_.data_ptr() + beg;
-      if (!pre) cast_f32_bf16((const float*)grad_.data_ptr() + beg, gb, (int64_t)n, comm_stream_);
-      comm_->all_reduce_raw(gb, n, ncclBfloat16, ncclSum, comm_stream_);
+    comm_->all_reduce_raw(rccl_wire(beg, n, pre, st), (size_t)n, wire_type(), ncclSum, st);
+  }
+  // Sum reduce-scatter of world() * S gradients at beg into this rank's shard of them: RCCL when
+  // present, else IPC
+  void reduce_scatter_grads(int64_t beg, int64_t S, bool pre, hipStream_t st) {
+    void* shard = grad_wire(beg + rank_in_comm() * S);
+    if (comm_) {
+      comm_->reduce_scatter_raw(rccl_wire(beg, world() * S, pre, st), shard, (size_t)S, wire_type(), ncclSum, st);
     } else {
-      comm_->all_reduce_raw((float*)grad_.data_ptr() + beg, n, ncclFloat32, ncclSum, comm_stream_);
+      ipc_->reduce_scatter_raw(grad_src(beg, pre), pre, shard, bf16_comm_, S, 1.0, st);
     }
   }
 
@@ -1190,10 +1118,10 @@ class MnistEngine : public torch::CustomClassHolder {
   at::Tensor data_, labels_, perm_, rows_, xpre_, ypre_, dbg_;
   at::Tensor f1_, f2_, fhd_, fdh_, fdz2_, fslab_, fwg2_;  // fp32-mode activations / slabs
   bool fp32_ = false;
-  hipStream_t comm_stream_ = nullptr;
-  hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr, ev_done_ = nullptr;
-  hipStream_t opt_stream_ = nullptr;  // train_step_dp: the fc-region optimizer
-  hipEvent_t ev_opt_a_ = nullptr, ev_start_ = nullptr, ev_ag_ = nullptr;
+  HipStream comm_stream_;
+  HipEvent ev_a_, ev_b_, ev_done_;
+  HipStream opt_stream_;  // train_step_dp: the fc-region optimizer
+  HipEvent ev_opt_a_, ev_start_, ev_ag_;
   bool zero_ = false;
   bool merge_tail_ = false;
   bool pending_wag_ = false;  // serialized ZeRO: this step's shards not yet all-gathered
@@ -1205,7 +1133,7 @@ class MnistEngine : public torch::CustomClassHolder {
   bool sfb_ = false;
   at::Tensor sfp2_, sfdr_;
   int64_t sfb_rs_ = 0;
-  hipEvent_t ev_p2_ = nullptr, ev_wag_ = nullptr;
+  HipEvent ev_p2_, ev_wag_;
   // one GPU + Adam: the optimizer kernel also reduces the conv gradient slabs and bumps the step
   bool fuse_tail_ = true;
   bool local_bf16_grads_ = false;
@@ -1216,7 +1144,7 @@ class MnistEngine : public torch::CustomClassHolder {
   std::set<hipGraphNode_t> topo_seen_;
   std::vector<std::pair<std::string, std::vector<hipGraphNode_t>>> topo_tags_;
   std::string drop_wait_;  // fault injection for the topology test: this named wait is skipped
-  hipEvent_t pev_[P_N] = {};
+  HipEvent pev_[P_N];
   bool timing_ = false, timed_ = false, timed_dp_ = false;
 };
 

@@ -133,6 +133,36 @@ def test_forced_dp_world1_zero1_tracks_plain_dp(cuda, mode, sfb):
     tr1.close()
 
 
+def test_zero1_with_fp32_dtype_raises_before_launching(cuda):
+    """ZeRO-1 is a bf16-path option: with ``set_dtype("fp32")`` an eager step and a capture both
+    raise on the host before anything is launched (the sharded step would read the stale bf16
+    shadow), the failed capture leaves the stream out of capture mode, and back in bf16 the engine
+    steps, captures and replays as if nothing had happened."""
+    from tensorflow_distributed_amd.parallel.transport import attach_engine
+
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        params, (zr,) = _engines_on_dataset(cuda, 1, B=32)
+        tr = attach_engine(zr, 0, 1, cuda, mode="ipc", force_dp=True)
+        zr.set_zero(True)
+        zr.train_step()
+        zr.set_dtype("fp32")
+        with pytest.raises(RuntimeError, match="ZeRO"):
+            zr.train_step()
+        with pytest.raises(RuntimeError, match="ZeRO"):
+            zr.capture_train_steps("x", 2)
+        step0 = int(zr.step_tensor().item())
+        zr.set_dtype("bf16")
+        zr.train_step()
+        zr.capture_train_steps("x", 2)
+        zr.replay("x", 1)
+    torch.cuda.synchronize()
+    tr.check()
+    assert step0 == 1 and int(zr.step_tensor().item()) == step0 + 3
+    assert torch.isfinite(zr.params()).all()
+    tr.close()
+
+
 @pytest.mark.parametrize("mode,sfb,zero,mr", [("rccl", True, False, False), ("ipc", True, False, False),
                                               ("rccl", True, True, False), ("rccl", True, False, True),
                                               ("ipc", True, False, True), ("rccl", True, True, True),

@@ -331,7 +331,13 @@ def test_resnet_rccl_bucketed_world1_equals_no_comm(cuda, row_mode, bf16, small_
     CUDAGraph.replay): RcclComm's destructor no longer destroys a communicator that an earlier
     test's still-alive captured graph used (see test_rccl_comm_outlives_its_python_object).
     small_ipc: the small buckets ride the IPC one-shot all-reduce beside RCCL (a world-1 IpcComm)."""
+    import gc
+
     n_bad, names, finite = _rccl_bucketed_worker(0, 1, bf16, small_ipc)
+    # the models' layers point back at them (reference cycles): collect them and their communicator
+    # here, where nothing is capturing, not whenever the collector next runs (a communicator
+    # destroyed inside a later capture invalidates that capture)
+    gc.collect()
     assert finite
     assert n_bad == 0, f"{n_bad} parameters differ (first in {names})"
 
