@@ -59,6 +59,50 @@ def probe(candidates: Sequence[str], run_one: Callable[[str], float], max_over_r
     return out
 
 
+def timed_probe(setup: Callable[[], None], warmup: Callable[[], None], timed: Callable[[], float],
+                teardown: Callable[[], None], *, max_over_ranks: Callable[[float], float],
+                barrier: Callable[[], None], what: str = "schedule probe") -> float:
+    """One candidate's probe on this rank -> local ms/step (what ``timed`` returns); the ``run_one`` of
+    :func:`probe`. The four callables hold everything device-specific and no collective of the probe
+    protocol; every rank runs the same sequence of ``max_over_ranks`` / ``barrier`` calls whichever
+    section raises where, and a section's failure on one rank is raised as RuntimeError on every rank:
+
+    1. ``setup`` (engine, transport, data), then agree. On failure ``teardown`` (which has to cope
+       with a half-done setup; no peer has used this rank's resources yet) and raise.
+    2. ``warmup`` (untimed steps), then agree -- BEFORE the barrier that opens the timed section, so a
+       rank whose warm-up raised does not leave its peers alone in that barrier. On failure the
+       teardown of step 5, then raise.
+    3. ``barrier``; 4. ``timed`` (the timed steps and the transport's health check).
+    5. ``barrier`` (a peer may still read this rank's resources), ``teardown``, ``barrier``.
+    6. Agree on the timed section's error; raise or return.
+
+    ``warmup`` and ``timed`` leave the device idle when they return or raise."""
+    def release() -> None:
+        barrier()
+        try:
+            teardown()
+        finally:
+            barrier()
+
+    def section(name: str, fn, then=lambda: None, on_failure=lambda: None):
+        """Run ``fn``, then ``then``, then agree: a failure on any rank cleans up and raises on every rank."""
+        out = err = None
+        try:
+            out = fn()
+        except Exception as e:  # noqa: BLE001 - agreed on by every rank right below
+            err = e
+        then()
+        if max_over_ranks(1.0 if err is not None else 0.0) > 0:
+            on_failure()
+            raise RuntimeError(f"{what}: {name} failed on a worker (here: {err!r})")
+        return out
+
+    section("setup", setup, on_failure=teardown)
+    section("warmup", warmup, on_failure=release)
+    barrier()
+    return section("timed", timed, then=release)
+
+
 def pick(times: Dict[str, float]) -> str:
     """Fastest candidate; ties go to the earlier candidate (dict order = probe order). Raises if no
     candidate produced a finite time."""

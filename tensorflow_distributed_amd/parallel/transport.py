@@ -165,6 +165,7 @@ class DPTransport:
         self.kind = kind  # "none" | "rccl" | "rccl+ipc" | "ipc"
         self.comm = comm
         self.ipc = ipc
+        self.zero = False  # attach_schedule: the engine shards fc1 (ZeRO-1)
 
     def error(self) -> int:
         """Sticky IPC barrier-timeout word (0 = healthy). A timeout leaves that collective's output
@@ -267,3 +268,22 @@ def attach_engine(eng, rank: int, world: int, device: torch.device, group=None, 
         if ipc is not None:
             ipc.close()
     return _sfb(DPTransport(kind, comm=comm))
+
+
+def attach_schedule(runner, name: Optional[str], rank: int, world: int, device: torch.device, *, group=None,
+                    src: int = 0, mode: str = "auto", comm=None, bf16: bool = True, dtype: str = "bf16") -> DPTransport:
+    """Wire ``runner`` (a native MNIST runner) for the DP schedule ``name`` of
+    ``schedule.MNIST_SCHEDULES`` (an unknown name or None: every switch off): the transport of
+    :func:`attach_engine`, the engine's ZeRO-1 and merged-reduce switches, and ``runner.comm`` /
+    ``runner.transport``. Sufficient factors and ZeRO-1 are bf16 schedules: with ``dtype`` fp32 both stay off."""
+    from .schedule import MNIST_SCHEDULES
+
+    cfg = MNIST_SCHEDULES.get(name, {"fc_sfb": 0, "zero": 0, "merge_reduce": 0})
+    sfb, zero = (bool(cfg[k]) and dtype == "bf16" for k in ("fc_sfb", "zero"))
+    tr = attach_engine(runner.eng, rank, world, device, group=group, src=src, mode=mode, comm=comm, bf16=bf16,
+                       sfb=sfb, zero=zero)
+    runner.comm, runner.transport, tr.zero = tr.comm, tr, zero
+    if zero:
+        runner.eng.set_zero(True)
+    runner.eng.set_sfb_merge_reduce(bool(cfg["merge_reduce"]))
+    return tr

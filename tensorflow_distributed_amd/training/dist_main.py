@@ -10,7 +10,9 @@ Roles:
     reaches ``--train_steps``; then a 5 x 1000 validation pass.
 
 Sync mode = all-reduce DP with SyncReplicasOptimizer semantics (parallel/sync_replicas.py); async
-mode = Hogwild PS over Gloo point-to-point (parallel/async_ps.py).
+mode = Hogwild PS over Gloo point-to-point (parallel/async_ps.py). ``main`` resolves the roles once and
+hands over to ``_run_ps``, ``_mnist_worker`` or ``_resnet_worker``; how the MNIST worker synchronises
+gradients is one object of training/grad_sync.py.
 """
 from __future__ import annotations
 
@@ -18,10 +20,14 @@ import os
 import sys
 import tempfile
 import time
+from typing import NamedTuple
 
-import numpy as np
 import torch
+import torch.distributed as dist
 
+from ..models import mnist_cnn as M
+from ..parallel import async_ps
+from ..parallel import schedule as SCH
 from ..utils import flags as flags_mod
 from ..utils.flags import FLAGS
 
@@ -199,8 +205,6 @@ def agree_gpu_ps(capable: bool, host: str, group=None):
     """All-gather (host identity, capable) over every ps and worker task of ``group``. Returns
     (use the GPU-resident PS, reason if not): yes only if every task is capable and all share one
     host; otherwise every task falls back to the host parameter server -- the same answer on all."""
-    import torch.distributed as dist
-
     rows = [(host, bool(capable))]
     if dist.is_initialized() and dist.get_world_size(group) > 1:
         rows = [None] * dist.get_world_size(group)
@@ -229,6 +233,74 @@ def _set_bn_mode(deterministic: bool) -> None:
         _native.ops().set_bn_part_slots(0)
 
 
+# ---- what the two workers share: the device, the reference's stdout around the training loop ----
+
+def _task_device() -> torch.device:
+    """GPU ``task_index % num_gpus`` (made the current device), or the CPU with --num_gpus=0."""
+    if FLAGS.num_gpus <= 0:
+        return torch.device("cpu")
+    torch.cuda.set_device(FLAGS.task_index % FLAGS.num_gpus)
+    return torch.device("cuda", FLAGS.task_index % FLAGS.num_gpus)
+
+
+def _prepare_session(cluster, is_chief: bool, runner, init_fn, broadcast):
+    """The Supervisor (mnist_python_m.py:235-253) with its session prepared: the chief initialises or restores,
+    then ``broadcast(sv)`` takes the chief's state to every worker."""
+    from .supervisor import Supervisor
+
+    sv = Supervisor(is_chief=is_chief, logdir=FLAGS.logdir or tempfile.mkdtemp(), runner=runner, init_fn=init_fn,
+                    broadcast_fn=lambda: broadcast(sv), save_model_secs=FLAGS.save_model_secs,
+                    save_summaries_secs=FLAGS.save_summaries_secs, recovery_wait_secs=1)
+    if is_chief:
+        print("Worker %d: Initializing session..." % FLAGS.task_index)
+    else:
+        print("Worker %d: Waiting for session to be initialized..." % FLAGS.task_index)
+    if FLAGS.existing_servers:
+        print("Using existing server at: %s" % ("grpc://" + cluster.task_address("worker", FLAGS.task_index)))
+    sys.stdout.flush()
+    sv.prepare_or_wait_for_session()
+    print("Worker %d: Session initialization complete." % FLAGS.task_index)
+    return sv
+
+
+def _training_begins() -> float:
+    time_begin = time.time()
+    print("Training begins @ %f" % time_begin)
+    return time_begin
+
+
+def _training_ends(time_begin: float, not_training: float = 0.0) -> float:
+    """Training time in seconds, without the ``not_training`` ones spent in --eval_at_steps passes."""
+    time_end = time.time()
+    print("Training ends @ %f" % time_end)
+    training_time = time_end - time_begin - not_training
+    print("Training elapsed time: %f s" % training_time)
+    return training_time
+
+
+def _validate(eval_batch) -> float:
+    """The reference's validation pass (5 x 1000 images, mnist_python_m.py:309-320) over --eval_batches
+    batches; ``eval_batch()`` evaluates the next one -> (images, correct). Returns the mean accuracy."""
+    accs = []
+    for _ in range(FLAGS.eval_batches):
+        n, correct = eval_batch()
+        print("After %d training step(s)", FLAGS.train_steps)  # verbatim reference line (quirk Q3)
+        print("Accuracy : %f" % (correct / float(n)))
+        accs.append(correct / float(n))
+    mean_accuracy = sum(accs) / len(accs) if accs else float("nan")
+    print("Mean Accuracy : %f" % mean_accuracy)
+    sys.stdout.flush()
+    return mean_accuracy
+
+
+def _leave(server, barrier_group=None) -> int:
+    server.mark_done()
+    if barrier_group is not None:
+        dist.barrier(group=barrier_group)
+    server.shutdown()
+    return 0
+
+
 def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
     """``--model resnet18|resnet50``: the same cluster roles, stdout and Supervisor services as the MNIST
     path, training the synthetic-ImageNet ResNet family (BASELINE configs 4-5) with synchronous DP --
@@ -241,19 +313,14 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
     global step go to every worker; timed checkpoints (``--save_model_secs``) in the MNIST layout
     (models/resnet.ResNetRunner); after training an inference-mode validation pass over
     ``--eval_batches`` synthetic batches and a final checkpoint."""
-    import torch.distributed as dist
-
     from ..models.resnet import ResNet, ResNetRunner
     from ..parallel.ipc import IpcCollectives, make_ipc_comm
     from ..parallel.transport import devices_shared, make_rccl
-    from .supervisor import Supervisor
 
     if not FLAGS.sync_replicas or FLAGS.num_gpus <= 0:
         raise ValueError("--model %s: synchronous data parallelism on GPUs only (--num_gpus > 0)" % FLAGS.model)
     _set_bn_mode(FLAGS.bn_deterministic)
-    gpu = FLAGS.task_index % FLAGS.num_gpus
-    torch.cuda.set_device(gpu)
-    device = torch.device("cuda", gpu)
+    device = _task_device()
     depth = int(FLAGS.model.replace("resnet", ""))
     m = ResNet(depth, num_classes=1000, device=device, seed=FLAGS.seed)
     runner = ResNetRunner(m)
@@ -261,12 +328,12 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
     grp = server.worker_group
     if num_workers > 1:
         if devices_shared(device, num_workers, grp):
-            comm = IpcCollectives(make_ipc_comm(FLAGS.task_index, num_workers, gpu, m.fp.total, group=grp))
+            comm = IpcCollectives(make_ipc_comm(FLAGS.task_index, num_workers, device.index, m.fp.total, group=grp))
         else:
-            comm = make_rccl(FLAGS.task_index, num_workers, gpu, group=grp, src=cluster.num_ps)
+            comm = make_rccl(FLAGS.task_index, num_workers, device.index, group=grp, src=cluster.num_ps)
     m.set_comm(comm, FLAGS.bucket_mb or 8.0)
 
-    def broadcast_fn():  # chief's (restored or seeded) state -> every worker (reference M6)
+    def broadcast(sv):  # chief's (restored or seeded) state -> every worker (reference M6)
         if num_workers <= 1:
             return
         for t in [m.fp.master, m.fp.momentum] + [b for bn in m.bns for b in (bn.rmean, bn.rvar)]:
@@ -278,23 +345,12 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
         dist.broadcast(st, cluster.num_ps, group=grp)
         runner.set_global_step(int(st.item()))
 
-    logdir = FLAGS.logdir or tempfile.mkdtemp()
-    sv = Supervisor(is_chief=is_chief, logdir=logdir, runner=runner, init_fn=lambda: None, broadcast_fn=broadcast_fn,
-                    save_model_secs=FLAGS.save_model_secs, save_summaries_secs=FLAGS.save_summaries_secs,
-                    recovery_wait_secs=1)
-    if is_chief:
-        print("Worker %d: Initializing session..." % FLAGS.task_index)
-    else:
-        print("Worker %d: Waiting for session to be initialized..." % FLAGS.task_index)
-    sys.stdout.flush()
-    sv.prepare_or_wait_for_session()
-    print("Worker %d: Session initialization complete." % FLAGS.task_index)
+    sv = _prepare_session(cluster, is_chief, runner, lambda: None, broadcast)
     S = FLAGS.image_size
     g = torch.Generator(device=device).manual_seed(100 + FLAGS.task_index)
     x = torch.randn(FLAGS.batch_size, S, S, 3, device=device, generator=g)
     y = torch.randint(0, 1000, (FLAGS.batch_size,), device=device, generator=g, dtype=torch.int32)
-    time_begin = time.time()
-    print("Training begins @ %f" % time_begin)
+    time_begin = _training_begins()
     local_step = 0
     step = runner.global_step()
     learning_rate = _make_learning_rate()  # a float or a schedule of the runner's global_step
@@ -308,25 +364,19 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
                 time.time(), FLAGS.task_index, local_step, step, float(loss)))
         sv.on_step(step)
     torch.cuda.synchronize(device)
-    time_end = time.time()
-    print("Training ends @ %f" % time_end)
-    el = time_end - time_begin
-    print("Training elapsed time: %f s" % el)
+    el = _training_ends(time_begin)
     print("Worker %d: %.1f images/sec (this worker)" % (FLAGS.task_index, FLAGS.batch_size * local_step / max(el, 1e-9)))
-    # validation (reference: 5 x 1000 images, mnist_python_m.py:309-320): synthetic batches of at most
-    # --batch_size images through the inference-mode network (running BN statistics)
+    # synthetic validation batches of at most --batch_size images through the inference-mode network
+    # (running BN statistics)
     gv = torch.Generator(device=device).manual_seed(7 + FLAGS.task_index)
-    accs = []
     nb = min(FLAGS.eval_batch_size, FLAGS.batch_size)
-    for _ in range(FLAGS.eval_batches):
+
+    def eval_batch():
         vx = torch.randn(nb, S, S, 3, device=device, generator=gv)
         vy = torch.randint(0, 1000, (nb,), device=device, generator=gv, dtype=torch.int32)
-        _, correct = m.evaluate(vx, vy)
-        print("After %d training step(s)", FLAGS.train_steps)  # verbatim reference line (quirk Q3)
-        print("Accuracy : %f" % (correct / float(nb)))
-        accs.append(correct / float(nb))
-    print("Mean Accuracy : %f" % (sum(accs) / len(accs) if accs else float("nan")))
-    sys.stdout.flush()
+        return nb, m.evaluate(vx, vy)[1]
+
+    _validate(eval_batch)
     if num_workers > 1:
         dist.barrier(group=grp)
     sv.stop(save=True)
@@ -334,14 +384,12 @@ def _resnet_worker(server, cluster, num_workers: int, is_chief: bool) -> int:
         if comm.ipc.error():
             raise RuntimeError("IPC collective barrier timed out")
         comm.ipc.close()
-    server.mark_done()
-    server.shutdown()
-    return 0
+    return _leave(server)
 
+
+# ---- --dp_schedule: which sync DP schedule (parallel/schedule.py) the workers train with ----
 
 def _max_over(group, v: float) -> float:
-    import torch.distributed as dist
-
     t = torch.tensor([float(v)], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return float(t.item())
@@ -349,8 +397,6 @@ def _max_over(group, v: float) -> float:
 
 def dp_candidates(device_type: str, dtype: str):
     """The sync DP schedules this worker device can run (parallel/schedule.py), in probe order."""
-    from ..parallel import schedule as SCH
-
     if device_type == "cuda":
         return list(SCH.MNIST_SCHEDULES) if dtype == "bf16" else ["allreduce"]
     return list(SCH.CPU_SCHEDULES)
@@ -363,8 +409,6 @@ def choose_dp_schedule(run_one, rank: int, num_workers: int, device_type: str, g
     ``run_one(name)`` (same names, same order), the slowest worker's time counts and all keep the
     fastest -- the same in-job probe as bench.py (parallel/schedule.py). The reference has one
     schedule, the PS star (/root/reference/mnist_python_m.py:177,210-233)."""
-    from ..parallel import schedule as SCH
-
     known = dp_candidates(device_type, FLAGS.dtype)
     want = FLAGS.dp_schedule
     if want == "fixed":
@@ -379,97 +423,141 @@ def choose_dp_schedule(run_one, rank: int, num_workers: int, device_type: str, g
     return SCH.pick(times), times, "probe"
 
 
+def _timed_probe(name, group, setup, warmup, timed, teardown) -> float:
+    """The probe protocol of parallel/schedule.py over the workers' Gloo group."""
+    return SCH.timed_probe(setup, warmup, timed, teardown, max_over_ranks=lambda v: _max_over(group, v),
+                           barrier=lambda: dist.barrier(group=group), what="schedule probe %s" % name)
+
+
 def _probe_gpu_schedule(name, mnist, device, num_workers, group, src, comm):
     """Local ms/step of one GPU DP schedule: a throwaway engine + transport on the worker's device,
     chief-style init, the device-resident split, --dp_probe_warmup untimed then --dp_probe_steps
-    timed graph replays between barriers. Setup failures are agreed on first (no worker may enter
-    the timing collectives alone)."""
-    import torch.distributed as dist
-
-    from ..models import mnist_cnn as M
+    timed graph replays."""
     from ..models.mnist_runner import make_runner
-    from ..parallel.schedule import MNIST_SCHEDULES
-    from ..parallel.transport import attach_engine
+    from ..parallel.transport import attach_schedule
 
-    cfg = MNIST_SCHEDULES.get(name, {"fc_sfb": 0, "zero": 0, "merge_reduce": 0})
-    r, tr, err = None, None, None
-    try:
+    r = None
+
+    def setup():
+        nonlocal r
         r = make_runner(FLAGS.batch_size, _make_optimizer(), device, keep_prob=FLAGS.keep_prob, seed=FLAGS.seed,
                         rank=FLAGS.task_index, bf16_grads=FLAGS.bf16_grads, use_graph=True, dtype=FLAGS.dtype)
-        tr = attach_engine(r.eng, FLAGS.task_index, num_workers, device, group=group, src=src, mode=FLAGS.dp_transport,
-                           comm=comm, bf16=FLAGS.bf16_grads, sfb=bool(cfg["fc_sfb"]) and FLAGS.dtype == "bf16",
-                           zero=bool(cfg["zero"]))
-        if cfg["zero"]:
-            r.eng.set_zero(True)
-        r.eng.set_sfb_merge_reduce(bool(cfg["merge_reduce"]))
-        r.comm, r.transport = tr.comm, tr
+        attach_schedule(r, name, FLAGS.task_index, num_workers, device, group=group, src=src,
+                        mode=FLAGS.dp_transport, comm=comm, bf16=FLAGS.bf16_grads, dtype=FLAGS.dtype)
         r.set_device_dataset(mnist.train.images, mnist.train.labels, seed=FLAGS.seed * 1000 + FLAGS.task_index + 31)
         r.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0)
-    except Exception as e:  # noqa: BLE001 - agreed below
-        err = e
-    if _max_over(group, 1.0 if err is not None else 0.0) > 0:
-        if tr is not None:
-            tr.close()
-        raise RuntimeError("schedule probe setup failed on a worker (here: %r)" % (err,))
-    try:
-        r.train_step(None, None)  # eager step + capture of the step graph
-        with torch.cuda.stream(r.stream):
-            r.eng.replay("train", max(1, FLAGS.dp_probe_warmup))
-        torch.cuda.synchronize(device)
-        dist.barrier(group=group)
-        t0 = time.perf_counter()
+
+    def replay(n: int, eager_first: bool = False):
+        try:
+            if eager_first:
+                r.train_step(None, None)  # eager step + capture of the step graph
+            with torch.cuda.stream(r.stream):
+                r.eng.replay("train", n)
+        finally:  # raised or not, the device is idle when the section ends
+            torch.cuda.synchronize(device)
+
+    def timed():
         n = max(1, FLAGS.dp_probe_steps)
-        with torch.cuda.stream(r.stream):
-            r.eng.replay("train", n)
-        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        replay(n)
         dt = time.perf_counter() - t0
-        tr.check("schedule probe %s" % name)
-    except Exception as e:  # noqa: BLE001 - agreed after the teardown barriers
-        err = e
-    torch.cuda.synchronize(device)
-    dist.barrier(group=group)  # a peer may still read this engine's IPC staging
-    r.eng.drop_graph("train")
-    tr.close()
-    dist.barrier(group=group)
-    # a timed-section failure (replay, or an IPC timeout caught by check) on one worker is raised on
-    # EVERY worker, so none goes on alone into the next candidate's collectives
-    if _max_over(group, 1.0 if err is not None else 0.0) > 0:
-        raise RuntimeError("schedule probe %s failed on a worker (here: %r)" % (name, err))
-    return dt * 1e3 / n
+        r.transport.check("schedule probe %s" % name)  # an IPC barrier timeout is a failed candidate
+        return dt * 1e3 / n
+
+    def teardown():
+        if r is not None:
+            r.eng.drop_graph("train")
+            if r.transport is not None:
+                r.transport.close()
+
+    return _timed_probe(name, group, setup, lambda: replay(max(1, FLAGS.dp_probe_warmup), eager_first=True), timed,
+                        teardown)
 
 
 def _probe_cpu_schedule(name, num_workers, group):
     """Local ms/step of one Gloo schedule on the CPU runner (random batch, 1 + min(5, steps) steps)."""
-    import torch.distributed as dist
-
-    from ..models import mnist_cnn as M
     from ..models.mnist_runner import TorchMnistRunner
     from ..parallel.sync_replicas import GlooGradAverager
 
-    r = TorchMnistRunner(FLAGS.batch_size, _make_optimizer(), FLAGS.keep_prob, FLAGS.seed, FLAGS.task_index)
-    r.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0)
-    r.comm = GlooGradAverager(group, num_workers, [M.BUCKET_SPLIT] if name == "buckets" else None)
-    g = torch.Generator().manual_seed(FLAGS.task_index + 5)
-    x = torch.rand(FLAGS.batch_size, 784, generator=g)
-    y = torch.randint(0, 10, (FLAGS.batch_size,), generator=g)
-    r.train_step(x, y)
-    dist.barrier(group=group)
-    n = max(1, min(FLAGS.dp_probe_steps, 5))
-    t0 = time.perf_counter()
-    for _ in range(n):
-        r.train_step(x, y)
-    return (time.perf_counter() - t0) * 1e3 / n
+    r = x = y = None
+
+    def setup():
+        nonlocal r, x, y
+        r = TorchMnistRunner(FLAGS.batch_size, _make_optimizer(), FLAGS.keep_prob, FLAGS.seed, FLAGS.task_index)
+        r.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0)
+        r.comm = GlooGradAverager(group, num_workers, [M.BUCKET_SPLIT] if name == "buckets" else None)
+        g = torch.Generator().manual_seed(FLAGS.task_index + 5)
+        x = torch.rand(FLAGS.batch_size, 784, generator=g)
+        y = torch.randint(0, 10, (FLAGS.batch_size,), generator=g)
+
+    def timed():
+        n = max(1, min(FLAGS.dp_probe_steps, 5))
+        t0 = time.perf_counter()
+        for _ in range(n):
+            r.train_step(x, y)
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    return _timed_probe(name, group, setup, lambda: r.train_step(x, y), timed, lambda: None)
+
+
+def _choose_schedule(server, cluster, mnist, device, is_chief):
+    """All-reduce DP with more than one worker: which schedule -- probed in-job by every worker, or
+    fixed by --dp_schedule. One RCCL communicator serves every probe and the training run.
+    -> (schedule, {candidate: ms/step} or None, how it was chosen, the RCCL communicator or None)."""
+    num_workers, grp, rccl = cluster.num_workers, server.worker_group, None
+    if device.type == "cuda":
+        from ..parallel.transport import devices_shared, make_rccl
+
+        if FLAGS.dp_transport != "ipc" and not devices_shared(device, num_workers, grp):
+            rccl = make_rccl(FLAGS.task_index, num_workers, device.index or 0, group=grp, src=cluster.num_ps)
+        run_one = lambda name: _probe_gpu_schedule(name, mnist, device, num_workers, grp,  # noqa: E731
+                                                   cluster.num_ps, rccl)
+    else:
+        run_one = lambda name: _probe_cpu_schedule(name, num_workers, grp)  # noqa: E731
+    log = (lambda m: print(m, file=sys.stderr, flush=True)) if is_chief else None
+    dp_sched, dp_probe, dp_source = choose_dp_schedule(run_one, FLAGS.task_index, num_workers, device.type, grp, log)
+    if is_chief:
+        print("Worker %d: DP schedule %s (%s%s)" % (
+            FLAGS.task_index, dp_sched, dp_source,
+            (": " + ", ".join("%s %.4f ms/step" % kv for kv in dp_probe.items())) if dp_probe else ""))
+    return dp_sched, dp_probe, dp_source, rccl
+
+
+# ---- the roles ----
+
+class Roles(NamedTuple):
+    """How this job synchronises gradients, resolved once from the flags and the cluster (the same on
+    every task). ``ps_mode`` false: all-reduce DP (parallel/sync_replicas.py)."""
+    sync: bool        # --sync_replicas
+    r2a: int          # replicas to aggregate per update, at most the number of workers
+    backup_ps: bool   # backup workers (R < N) with a ps task: TF's accumulator semantics on the PS (stale
+    #                   gradients of stragglers dropped, the first R fresh ones averaged); without a ps task:
+    #                   the all-gather stepper
+    ps_mode: bool     # the variables live on the ps tasks: async, or backup_ps
+    use_gpu_ps: bool  # ... on the ps tasks' GPUs (parallel/gpu_ps.py)
+
+
+def _resolve_roles(num_workers: int, has_ps: bool) -> Roles:
+    sync = FLAGS.sync_replicas
+    r2a = num_workers
+    if sync:
+        r2a = FLAGS.replicas_to_aggregate if FLAGS.replicas_to_aggregate is not None else num_workers
+        if r2a > num_workers:
+            # TF1 would wait forever for gradients that never come; clamp instead (and say so)
+            print("Worker %d: replicas_to_aggregate=%d > %d workers; aggregating %d" %
+                  (FLAGS.task_index, r2a, num_workers, num_workers))
+            r2a = num_workers
+    backup_ps = sync and r2a < num_workers and has_ps
+    ps_mode = (not sync) or backup_ps
+    # GPU-resident PS only when EVERY task (ps and worker) can take part: same host (the data path is
+    # IPC peer memory) and a GPU on each. Decided collectively so the PS and the workers never pick
+    # different protocols (the reference's default cluster spans three hosts, mnist_python_m.py:81-84).
+    return Roles(sync, r2a, backup_ps, ps_mode, ps_mode and _agree_gpu_ps())
 
 
 def main(argv=None) -> int:
-    from ..models import mnist_cnn as M
-    from ..models.mnist_runner import make_runner
-    from ..parallel import async_ps, sync_replicas
     from ..parallel.cluster import ClusterSpec, Server
     from ..utils import input_data
-    from ..utils.metrics import MetricsLogger, StepTimer
-    from .optimizers import SyncReplicasOptimizer
-    from .supervisor import Supervisor
 
     if FLAGS.download_only:
         # no network on MI355X boxes: materialise the IDX files (synthetic if absent) and stop
@@ -490,222 +578,93 @@ def main(argv=None) -> int:
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
 
-    ps_spec = FLAGS.ps_hosts.split(",")
-    worker_spec = FLAGS.worker_hosts.split(",")
-    num_workers = len(worker_spec)
-    cluster = ClusterSpec({"ps": ps_spec, "worker": worker_spec})
-
+    cluster = ClusterSpec({"ps": FLAGS.ps_hosts.split(","), "worker": FLAGS.worker_hosts.split(",")})
     server = Server(cluster, job_name=FLAGS.job_name, task_index=FLAGS.task_index,
                     existing_servers=FLAGS.existing_servers, timeout_s=FLAGS.rendezvous_timeout)
     opt = _make_optimizer()
-    from .optimizers import lr_at
-
-    learning_rate = opt.learning_rate  # a float, or a schedule of global_step
     layout = async_ps.mnist_layout(cluster.num_ps) if cluster.num_ps else None
     if not FLAGS.sync_replicas and layout is None:
         raise ValueError("--sync_replicas=False (async parameter-server mode) needs at least one --ps_hosts task")
-
-    sync = FLAGS.sync_replicas
-    r2a = num_workers
-    if sync:
-        r2a = FLAGS.replicas_to_aggregate if FLAGS.replicas_to_aggregate is not None else num_workers
-        if r2a > num_workers:
-            # TF1 would wait forever for gradients that never come; clamp instead (and say so)
-            print("Worker %d: replicas_to_aggregate=%d > %d workers; aggregating %d" %
-                  (FLAGS.task_index, r2a, num_workers, num_workers))
-            r2a = num_workers
-    # backup workers (R < N) with a ps task: TF's accumulator semantics on the PS (stale gradients of
-    # stragglers dropped, the first R fresh ones averaged); without a ps task: the all-gather stepper
-    backup_ps = sync and r2a < num_workers and layout is not None
-    ps_mode = (not sync) or backup_ps
-
-    # GPU-resident PS only when EVERY task (ps and worker) can take part: same host (the data path is
-    # IPC peer memory) and a GPU on each. Decided collectively so the PS and the workers never pick
-    # different protocols (the reference's default cluster spans three hosts, mnist_python_m.py:81-84).
-    use_gpu_ps = ps_mode and _agree_gpu_ps()
-
+    roles = _resolve_roles(cluster.num_workers, layout is not None)
     if FLAGS.job_name == "ps":
-        # (reference quirk Q9: ps + existing_servers fell through to the worker code; a PS here
-        #  always serves and then exits once every worker has finished)
-        service = None
-        if use_gpu_ps:
-            from ..parallel.gpu_ps import GpuParameterServerService
-
-            ps_gpu = FLAGS.task_index % FLAGS.num_gpus
-            torch.cuda.set_device(ps_gpu)
-            service = GpuParameterServerService(FLAGS.task_index, cluster.num_ps, num_workers, layout, opt,
-                                                torch.device("cuda", ps_gpu), sync=backup_ps,
-                                                replicas_to_aggregate=r2a)
-        elif ps_mode:
-            service = async_ps.ParameterServerService(FLAGS.task_index, cluster.num_ps, num_workers, layout, opt,
-                                                      sync=backup_ps, replicas_to_aggregate=r2a)
-        server.join(service)
-        server.shutdown()
-        if service is not None and backup_ps:
-            print("ps %d: %d synchronous updates, %d stale gradients dropped" % (FLAGS.task_index, service.updates,
-                                                                               service.dropped))
-        return 0
-
-    is_chief = FLAGS.task_index == 0
+        return _run_ps(server, cluster, roles, layout, opt)
     if FLAGS.model != "mnist_cnn":
-        return _resnet_worker(server, cluster, num_workers, is_chief)
-    if FLAGS.num_gpus > 0:
-        gpu = FLAGS.task_index % FLAGS.num_gpus
-        torch.cuda.set_device(gpu)
-        device = torch.device("cuda", gpu)
-    else:
-        device = torch.device("cpu")
+        return _resnet_worker(server, cluster, cluster.num_workers, FLAGS.task_index == 0)
+    return _mnist_worker(server, cluster, roles, layout, opt, mnist)
 
-    sopt = None
-    if sync:
-        sopt = SyncReplicasOptimizer(opt, replicas_to_aggregate=r2a, total_num_replicas=num_workers).resolve(num_workers)
 
-    # Sync all-reduce DP: which schedule (parallel/schedule.py) -- probed in-job by every worker, or
-    # fixed by --dp_schedule. One RCCL communicator serves every probe and the training run.
-    dp_sched, dp_probe, dp_source, rccl = None, None, None, None
-    allreduce_dp = sync and num_workers > 1 and not backup_ps
-    if allreduce_dp:
-        grp = server.worker_group
-        if device.type == "cuda":
-            from ..parallel.transport import devices_shared, make_rccl
+def _run_ps(server, cluster, roles: Roles, layout, opt) -> int:
+    """(reference quirk Q9: ps + existing_servers fell through to the worker code; a PS here always
+    serves and then exits once every worker has finished)"""
+    service = None
+    if roles.use_gpu_ps:
+        from ..parallel.gpu_ps import GpuParameterServerService
 
-            if FLAGS.dp_transport != "ipc" and not devices_shared(device, num_workers, grp):
-                rccl = make_rccl(FLAGS.task_index, num_workers, device.index or 0, group=grp, src=cluster.num_ps)
-            run_one = lambda name: _probe_gpu_schedule(name, mnist, device, num_workers, grp,  # noqa: E731
-                                                       cluster.num_ps, rccl)
-        else:
-            run_one = lambda name: _probe_cpu_schedule(name, num_workers, grp)  # noqa: E731
-        log = (lambda m: print(m, file=sys.stderr, flush=True)) if is_chief else None
-        dp_sched, dp_probe, dp_source = choose_dp_schedule(run_one, FLAGS.task_index, num_workers, device.type,
-                                                           grp, log)
-        if is_chief:
-            print("Worker %d: DP schedule %s (%s%s)" % (
-                FLAGS.task_index, dp_sched, dp_source,
-                (": " + ", ".join("%s %.4f ms/step" % kv for kv in dp_probe.items())) if dp_probe else ""))
+        service = GpuParameterServerService(FLAGS.task_index, cluster.num_ps, cluster.num_workers, layout, opt,
+                                            _task_device(), sync=roles.backup_ps, replicas_to_aggregate=roles.r2a)
+    elif roles.ps_mode:
+        service = async_ps.ParameterServerService(FLAGS.task_index, cluster.num_ps, cluster.num_workers, layout, opt,
+                                                  sync=roles.backup_ps, replicas_to_aggregate=roles.r2a)
+    server.join(service)
+    server.shutdown()
+    if service is not None and roles.backup_ps:
+        print("ps %d: %d synchronous updates, %d stale gradients dropped" % (FLAGS.task_index, service.updates,
+                                                                           service.dropped))
+    return 0
+
+
+def _log_device_placement(gsync, cluster, device) -> None:
+    """--log_device_placement: where every variable and the compute live."""
+    names = ["global_step"] + [tf for _, tf, _ in M.PARAM_SPECS]
+    wdev = "/job:worker/task:%d/%s:%d" % (FLAGS.task_index, "gpu" if device.type == "cuda" else "cpu",
+                                          device.index or 0)
+    placed = gsync.placement(cluster, names, wdev)
+    for n in names:
+        print("%s: %s" % (n, placed[n]))
+    print("compute (conv_net, loss, gradients): %s; gradient sync: %s" % (wdev, gsync.describe()))
+
+
+def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
+    from ..models.mnist_runner import make_runner
+    from ..utils.metrics import MetricsLogger, StepTimer, performance_table
+    from ..utils.tracing import Watchdog, trace_range
+    from .grad_sync import make_grad_sync
+    from .optimizers import SyncReplicasOptimizer, lr_at
+
+    sync, num_workers, is_chief = roles.sync, cluster.num_workers, FLAGS.task_index == 0
+    learning_rate = opt.learning_rate  # a float, or a schedule of global_step
+    device = _task_device()
+    if sync:  # tf.train.SyncReplicasOptimizer's check of 1 <= replicas_to_aggregate <= total_num_replicas
+        SyncReplicasOptimizer(opt, replicas_to_aggregate=roles.r2a, total_num_replicas=num_workers).resolve(num_workers)
+
+    dp_sched = dp_probe = dp_source = rccl = None
+    if sync and num_workers > 1 and not roles.ps_mode:
+        dp_sched, dp_probe, dp_source, rccl = _choose_schedule(server, cluster, mnist, device, is_chief)
+    # the R < N all-gather stepper (backup workers without a ps task) steps eagerly
     runner = make_runner(FLAGS.batch_size, opt, device, keep_prob=FLAGS.keep_prob, seed=FLAGS.seed,
                          rank=FLAGS.task_index, comm=None, bf16_grads=FLAGS.bf16_grads,
-                         use_graph=FLAGS.use_graph and (sopt is None or not sopt.has_backup_workers or backup_ps),
-                         dtype=FLAGS.dtype)
-    comm = None
-    transport = None
-    zero = False
-    if allreduce_dp and device.type == "cuda":
-        from ..parallel.schedule import MNIST_SCHEDULES
-        from ..parallel.transport import attach_engine
+                         use_graph=FLAGS.use_graph and (roles.ps_mode or roles.r2a >= num_workers), dtype=FLAGS.dtype)
+    if dp_sched is not None and device.type == "cuda":
+        from ..parallel.transport import attach_schedule
 
-        cfg = MNIST_SCHEDULES.get(dp_sched, {"fc_sfb": 0, "zero": 0, "merge_reduce": 0})
-        zero = bool(cfg["zero"]) and FLAGS.dtype == "bf16"
-        transport = attach_engine(runner.eng, FLAGS.task_index, num_workers, device, group=server.worker_group,
-                                  src=cluster.num_ps, mode=FLAGS.dp_transport, comm=rccl, bf16=FLAGS.bf16_grads,
-                                  sfb=bool(cfg["fc_sfb"]) and FLAGS.dtype == "bf16", zero=zero)
-        if zero:
-            runner.eng.set_zero(True)
-        runner.eng.set_sfb_merge_reduce(bool(cfg["merge_reduce"]))
-        comm = transport.comm
-        runner.comm = comm
-        runner.transport = transport
-    # PS modes overwrite the runner's step with the PS global step after every push, and the device
-    # permutation is indexed by that step: each worker would see ~1/N of its epoch. Those modes keep
-    # the reference's per-worker sequential next_batch (mnist_python_m.py:291) on the host instead.
-    device_input = device.type == "cuda" and FLAGS.device_input and not ps_mode
+        attach_schedule(runner, dp_sched, FLAGS.task_index, num_workers, device, group=server.worker_group,
+                        src=cluster.num_ps, mode=FLAGS.dp_transport, comm=rccl, bf16=FLAGS.bf16_grads,
+                        dtype=FLAGS.dtype)
+    transport = getattr(runner, "transport", None)  # the GPU all-reduce DP transport (RCCL / IPC)
+    zero = transport is not None and transport.zero
+    gsync = make_grad_sync(runner, cluster, roles, layout, opt, server.worker_group, dp_sched)
+    device_input = device.type == "cuda" and FLAGS.device_input and gsync.device_input
     if device_input:
         runner.set_device_dataset(mnist.train.images, mnist.train.labels,
                                   seed=FLAGS.seed * 1000 + FLAGS.task_index + 31)
 
-    def init_fn():
-        flat = M.flat_from_dict(M.init_params(FLAGS.seed))
-        runner.load_flat(flat, {}, 0)
-
-    client = None
-    gpu_ps = use_gpu_ps
-    if not ps_mode:
-        def broadcast_fn():
-            if num_workers > 1:
-                sync_replicas.broadcast_state(runner, 0, group=server.worker_group, group_src_rank=cluster.num_ps)
-    elif gpu_ps:
-        from ..parallel.gpu_ps import GpuPSClient
-        from .optimizers import FlatApplier
-
-        client = GpuPSClient(FLAGS.task_index, layout, runner.params(), runner.sync_shadow,
-                             slot_names=list(FlatApplier(opt, 0).slots()))
-        runner.ps_client = client  # the chief's checkpoints read the PS-resident state (params + slots)
-
-        def broadcast_fn():
-            if is_chief:
-                # the ps tasks read the initial / restored values from the chief's engine (peer memory);
-                # restored moments follow as host tensors, fresh ones start at zero
-                slots = {("m" if k == "accum" else k): v.detach().float().cpu()
-                         for k, v in runner.slot_tensors().items()} if sv.restored_from else None
-                client.init(step=runner.global_step(), t=runner.global_step(), slots=slots)
-            runner.set_global_step(client.pull())
-    else:
-        from .optimizers import FlatApplier
-
-        client = async_ps.AsyncPSClient(FLAGS.task_index, layout, slot_names=list(FlatApplier(opt, 0).slots()))
-        runner.ps_client = client  # the chief's checkpoints read the PS-resident state (params + slots)
-
-        def broadcast_fn():
-            flat = runner.params().detach().float().cpu()
-            if is_chief:
-                # restored moments go back to the PS (fresh init: zeros); t = global_step
-                slots = {("m" if k == "accum" else k): v.detach().float().cpu()
-                         for k, v in runner.slot_tensors().items()} if sv.restored_from else None
-                client.init(flat, step=runner.global_step(), t=runner.global_step(), slots=slots)
-            gs = client.pull(flat)
-            runner.set_params(flat)
-            runner.set_global_step(gs)
-
-    logdir = FLAGS.logdir or tempfile.mkdtemp()
-    sv = Supervisor(is_chief=is_chief, logdir=logdir, runner=runner, init_fn=init_fn, broadcast_fn=broadcast_fn,
-                    save_model_secs=FLAGS.save_model_secs, save_summaries_secs=FLAGS.save_summaries_secs,
-                    recovery_wait_secs=1)
-
-    if is_chief:
-        print("Worker %d: Initializing session..." % FLAGS.task_index)
-    else:
-        print("Worker %d: Waiting for session to be initialized..." % FLAGS.task_index)
-    if FLAGS.existing_servers:
-        server_grpc_url = "grpc://" + worker_spec[FLAGS.task_index]
-        print("Using existing server at: %s" % server_grpc_url)
-    sys.stdout.flush()
-    sv.prepare_or_wait_for_session()
-    print("Worker %d: Session initialization complete." % FLAGS.task_index)
-
+    sv = _prepare_session(cluster, is_chief, runner,
+                          lambda: runner.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0), gsync.broadcast)
     if FLAGS.log_device_placement:
-        from ..parallel.cluster import replica_device_setter
-
-        names = ["global_step"] + [tf for _, tf, _ in M.PARAM_SPECS]
-        wdev = "/job:worker/task:%d/%s:%d" % (FLAGS.task_index, "gpu" if device.type == "cuda" else "cpu",
-                                              device.index or 0)
-        placed = replica_device_setter(cluster, names, wdev) if ps_mode else {n: wdev + " (replicated)" for n in names}
-        if gpu_ps:  # each ps task's shard lives on its GPU (task % num_gpus), not on the reference's ps cpu
-            from ..parallel.cluster import ps_task_of
-
-            placed = {n: "/job:ps/task:%d/gpu:%d" % (ps_task_of(placed, n), ps_task_of(placed, n) % FLAGS.num_gpus)
-                      for n in names}
-        for n in names:
-            print("%s: %s" % (n, placed[n]))
-        print("compute (conv_net, loss, gradients): %s; gradient sync: %s" % (
-            wdev, (("GPU ps mailbox push / peer-memory pull" if gpu_ps else "async PS push/pull") if not sync else
-                   "PS accumulator (%d of %d replicas)" % (r2a, num_workers) if backup_ps else
-                   (transport.kind.replace("+sfb", "") + " all-reduce"
-                    + (" (fc layers: all-gathered sufficient factors)" if "+sfb" in transport.kind else ""))
-                   if transport is not None else "Gloo all-reduce")))
+        _log_device_placement(gsync, cluster, device)
 
     eval_at = sorted(int(v) for v in FLAGS.eval_at_steps.split(",") if v.strip()) if FLAGS.eval_at_steps else []
-    eval_time = 0.0
-    perf_rows = []
-
-    delays = {}
-    if FLAGS.straggler_delay:
-        for item in FLAGS.straggler_delay.split(","):
-            k, v = item.split(":")
-            delays[int(k)] = float(v)
-    stepper = None
-    if sync and not backup_ps:
-        stepper = sync_replicas.SyncReplicasStepper(runner, FLAGS.task_index, num_workers, sopt.replicas_to_aggregate,
-                                                    group=server.worker_group, straggler_delay_s=delays,
-                                                    splits=[M.BUCKET_SPLIT] if dp_sched == "buckets" else None)
+    eval_time, perf_rows = 0.0, []
     metrics = MetricsLogger(FLAGS.metrics_file if is_chief else "")
     if dp_sched is not None:
         metrics.log(event="dp_schedule", chosen=dp_sched, source=dp_source,
@@ -715,18 +674,17 @@ def main(argv=None) -> int:
         runner.set_phase_timing(True)
     timer = StepTimer(pid=FLAGS.task_index, enabled=bool(FLAGS.trace_file))
     restart_attempt = int(os.environ.get("TFD_RESTART_COUNT", "0"))
+    dp_comm = transport.comm if transport is not None else None  # RCCL; the IPC transport has nothing to abort
+    watchdog = Watchdog(FLAGS.step_timeout_secs, on_timeout=(dp_comm.abort if dp_comm is not None else None))
 
-    from ..utils.tracing import Watchdog, trace_range
+    def eval_batch():
+        val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
+        return len(val_x), runner.evaluate(val_x, val_y)[1]
 
-    watchdog = Watchdog(FLAGS.step_timeout_secs, on_timeout=(comm.abort if comm is not None else None))
-    time_begin = time.time()
-    print("Training begins @ %f" % time_begin)
+    time_begin = _training_begins()
     local_step = 0
     step = runner.global_step()
-    grad_cpu = None
-    while True:
-        if step >= FLAGS.train_steps:
-            break
+    while step < FLAGS.train_steps:
         with timer.phase("input"):
             if device_input:
                 batch_xs = batch_ys = None  # the engine gathers the batch on the device
@@ -734,44 +692,18 @@ def main(argv=None) -> int:
                 batch_xs, batch_ys = mnist.train.next_batch(FLAGS.batch_size)
         t0 = time.time()
         with timer.phase("step"), trace_range("train_step"):
-            if not ps_mode:
-                stepper.step(batch_xs, batch_ys)
-                step = runner.global_step()
-            elif gpu_ps:
-                g, _ = runner.compute_grads(batch_xs, batch_ys, with_loss=False)
-                if FLAGS.task_index in delays:
-                    time.sleep(delays[FLAGS.task_index])  # test hook: a straggling worker
-                # the gradient goes GPU -> the ps tasks' GPU mailboxes, the fresh values come back into
-                # the engine's parameters; only the 32-byte control messages touch the host
-                step = client.push_pull(g, local_step=step)
-                runner.set_global_step(step)
-            else:
-                g, _ = runner.compute_grads(batch_xs, batch_ys)
-                if grad_cpu is None:
-                    grad_cpu = torch.zeros(M.TOTAL)
-                grad_cpu.copy_(g.detach().float().cpu())
-                if FLAGS.task_index in delays:
-                    time.sleep(delays[FLAGS.task_index])  # test hook: a straggling worker
-                flat = runner.params().detach().float().cpu()
-                # sync: the gradient is tagged with the global step it was computed at (stale ones
-                # are dropped by the PS accumulator); async: applied as it comes
-                step = client.push_pull(flat, grad_cpu, local_step=step)
-                runner.set_params(flat)
-                runner.set_global_step(step)
+            step = gsync.step(batch_xs, batch_ys, step)
         local_step += 1
         watchdog.kick()
         now = time.time()
         if not FLAGS.quiet:
             print("%f: Worker %d: training step %d done (global step: %d)" % (now, FLAGS.task_index, local_step, step))
-            if backup_ps and client.last_dropped:
+            if gsync.last_dropped:
                 print("Worker %d: stale gradient dropped (a backup replica finished this step first)" % FLAGS.task_index)
         if metrics.path:
             rec = dict(step=local_step, global_step=step, step_ms=1e3 * (now - t0), loss=runner.last_loss(),
                        images_per_sec=FLAGS.batch_size * (num_workers if sync else 1) / max(now - t0, 1e-9))
-            if not ps_mode:
-                # lr of the update that produced this global step, from the host's step mirror (no device
-                # read). Not logged in the parameter-server modes: there every ps shard evaluates the
-                # schedule at its own update count, which is not this worker's global step
+            if gsync.logs_lr:
                 rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
             if phase_timing:
                 ph = runner.phase_times()
@@ -789,8 +721,6 @@ def main(argv=None) -> int:
             save_now = False
             if step % max(1, FLAGS.zero_sync_every) == 0:
                 due = torch.tensor([1 if sv.save_due() else 0], dtype=torch.int64)
-                import torch.distributed as dist
-
                 dist.all_reduce(due, op=dist.ReduceOp.MAX, group=server.worker_group)
                 save_now = bool(due.item())
                 if save_now:
@@ -800,10 +730,7 @@ def main(argv=None) -> int:
             sv.on_step(step)
         while is_chief and eval_at and step >= eval_at[0]:
             te = time.time()
-            accs = []
-            for _ in range(FLAGS.eval_batches):
-                vx, vy = mnist.validation.next_batch(FLAGS.eval_batch_size)
-                accs.append(runner.evaluate(vx, vy)[1] / float(len(vx)))
+            accs = [correct / float(n) for n, correct in (eval_batch() for _ in range(FLAGS.eval_batches))]
             acc = 100.0 * sum(accs) / len(accs)
             eval_time += time.time() - te
             row = dict(steps=eval_at.pop(0), time=time.time() - time_begin - eval_time, accuracy=round(acc, 2),
@@ -820,57 +747,33 @@ def main(argv=None) -> int:
     if zero:
         runner.sync_state()  # whole replicas again: final checksum, eval and the chief's last checkpoint
     if FLAGS.check_consistency_every and sync:
-        pp = runner.params().detach().double()
-        print("Worker %d: parameter checksum %.17g %.17g" % (FLAGS.task_index, float(pp.sum().item()),
-                                                             float((pp * pp).sum().item())))
+        print("Worker %d: parameter checksum %.17g %.17g" % ((FLAGS.task_index,) + _param_checksum(runner)))
     if transport is not None:
         transport.check("training")  # a timed-out IPC barrier must not pass as a finished run
-    time_end = time.time()
-    print("Training ends @ %f" % time_end)
-    training_time = time_end - time_begin - eval_time
-    print("Training elapsed time: %f s" % training_time)
-
-    accuracy_arr = []
-    nt = FLAGS.eval_batches
-    for counter in range(1, nt + 1):
-        val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
-        _, correct = runner.evaluate(val_x, val_y)
-        val_xent = correct / float(len(val_x))
-        print("After %d training step(s)", FLAGS.train_steps)  # verbatim reference line (quirk Q3)
-        print("Accuracy : %f" % val_xent)
-        accuracy_arr.append(val_xent)
-    mean_accuracy = sum(accuracy_arr) / len(accuracy_arr) if accuracy_arr else float("nan")
-    print("Mean Accuracy : %f" % mean_accuracy)
-    sys.stdout.flush()
-
+    training_time = _training_ends(time_begin, eval_time)
+    mean_accuracy = _validate(eval_batch)
     metrics.log(event="final", global_step=step, training_time_s=training_time, mean_accuracy=mean_accuracy)
     if perf_rows:
-        from ..utils.metrics import performance_table
-
         print(performance_table(perf_rows), end="")
     metrics.close()
     if FLAGS.trace_file:
         timer.write_chrome_trace(FLAGS.trace_file.replace("{task}", str(FLAGS.task_index)))
     sv.stop(save=True)
-    if client is not None:
-        client.stop()
+    gsync.close()
     if transport is not None:
         transport.close()
-    server.mark_done()
-    if sync and num_workers > 1:
-        import torch.distributed as dist
+    return _leave(server, server.worker_group if sync and num_workers > 1 else None)
 
-        dist.barrier(group=server.worker_group)
-    server.shutdown()
-    return 0
+
+def _param_checksum(runner):
+    """(sum, sum of squares) of the parameters in fp64."""
+    p = runner.params().detach().double()
+    return float(p.sum().item()), float((p * p).sum().item())
 
 
 def _check_consistency(runner, server, num_workers):
     """Race/desync detector: max |checksum_i - checksum_0| across workers."""
-    import torch.distributed as dist
-
-    p = runner.params().detach().double()
-    cs = torch.tensor([float(p.sum().item()), float((p * p).sum().item())], dtype=torch.float64)
+    cs = torch.tensor(_param_checksum(runner), dtype=torch.float64)
     mx, mn = cs.clone(), cs.clone()
     dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=server.worker_group)
     dist.all_reduce(mn, op=dist.ReduceOp.MIN, group=server.worker_group)
@@ -886,3 +789,4 @@ def run_script(task_index_default: int, job_name_default: str, argv=None) -> int
         return 0
     FLAGS.parse(argv)
     return main(argv) or 0
+
