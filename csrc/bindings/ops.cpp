@@ -30,11 +30,18 @@ LrSchedule flat_schedule(double lr, const std::string& kind, const std::vector<d
   }
 }
 
+// the optional trailing gscale of the flat optimizers: the device clip factor, one fp32 element (a
+// one-element view such as grad_global_norm(...)[1:2]) that multiplies grad_scale inside the kernel
+const float* clip_factor(const at::Tensor& t, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == 1, who, ": gscale is one fp32 GPU element");
+  return (const float*)t.data_ptr();
+}
+
 // Adam's t = *step + t_offset; the schedule is evaluated on the device at s = t - 1
 void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf, double lr,
                double b1, double b2, double eps, at::Tensor step, double grad_scale, int64_t t_offset,
                std::string lr_kind, std::vector<double> lr_params, std::vector<int64_t> lr_boundaries,
-               std::vector<double> lr_values) {
+               std::vector<double> lr_values, c10::optional<at::Tensor> gscale) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "adam_flat: fp32 GPU params");
   TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel() && g.numel() == p.numel(), "adam_flat: sizes");
   TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam_flat: int64 GPU step");
@@ -43,13 +50,15 @@ void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::opti
              pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
              flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
              (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
-  adam_apply(a, cur());
+  if (gscale) adam_apply_clip(AdamClipArgs{a, clip_factor(*gscale, "adam_flat")}, cur());
+  else adam_apply(a, cur());
 }
 
 void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
                    double lr, double momentum, double weight_decay, bool nesterov, double grad_scale,
                    c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind, std::vector<double> lr_params,
-                   std::vector<int64_t> lr_boundaries, std::vector<double> lr_values) {
+                   std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
+                   c10::optional<at::Tensor> gscale) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "momentum_flat: fp32 GPU params");
   TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), "momentum_flat: int64 GPU step");
   const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
@@ -59,7 +68,23 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
             pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
             sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
             step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
-  sgd_apply(a, cur());
+  if (gscale) sgd_apply_clip(SgdClipArgs{a, clip_factor(*gscale, "momentum_flat")}, cur());
+  else sgd_apply(a, cur());
+}
+
+// {norm, scale} of tf.clip_by_global_norm over a flat fp32 or bf16 buffer, on the device:
+// norm = grad_scale * sqrt(sum g^2), scale = clip_norm / max(norm, clip_norm) (grad_norm.hip)
+at::Tensor grad_global_norm(const at::Tensor& g, double clip_norm, double grad_scale) {
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && (gb || g.scalar_type() == at::kFloat) && g.is_contiguous() && g.numel() >= 1,
+              "grad_global_norm: a contiguous fp32 or bf16 GPU tensor of at least one element");
+  auto out = at::empty({2}, g.options().dtype(at::kFloat));
+  auto part = at::empty({kGradNormMaxBlocks}, out.options());
+  grad_sumsq(gb ? nullptr : (const float*)g.data_ptr(), gb ? (const uint16_t*)g.data_ptr() : nullptr, g.numel(),
+             (float*)part.data_ptr(), cur());
+  grad_norm_finish((const float*)part.data_ptr(), grad_norm_blocks(g.numel()), (float)grad_scale, (float)clip_norm,
+                   (float*)out.data_ptr(), cur());
+  return out;
 }
 
 void roofline_stream(at::Tensor p, at::Tensor m, at::Tensor v, const at::Tensor& g, at::Tensor pbf,
@@ -102,12 +127,15 @@ TORCH_LIBRARY(tfd, m) {
   m.impl("crc32c", c10::DispatchKey::CPU, &crc32c_op);
   m.def("adam_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, float lr, float b1, float b2, "
         "float eps, Tensor(e!) step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
-        "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[]) -> ()");
+        "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], Tensor? gscale=None) -> ()");
   m.impl("adam_flat", c10::DispatchKey::CUDA, &adam_flat);
   m.def("momentum_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
         "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
-        "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[]) -> ()");
+        "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
+        "Tensor? gscale=None) -> ()");
   m.impl("momentum_flat", c10::DispatchKey::CUDA, &momentum_flat);
+  m.def("grad_global_norm(Tensor g, float clip_norm, float grad_scale=1.0) -> Tensor");
+  m.impl("grad_global_norm", c10::DispatchKey::CUDA, &grad_global_norm);
   m.def("roofline_stream(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!) pbf, Tensor? x, int blocks, "
         "int unroll) -> ()");
   m.impl("roofline_stream", c10::DispatchKey::CUDA, &roofline_stream);

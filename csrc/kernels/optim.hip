@@ -96,18 +96,8 @@ void adam_apply(const AdamArgs& a, hipStream_t s) {
   else adam_apply_sched(a, s);
 }
 void adam_apply_ranges(const AdamArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s) {
-  if (nr < 1 || nr > 3) throw std::runtime_error("adam_apply_ranges: 1..3 ranges");
-  AdamRanges r{};
-  r.nr = nr;
-  r.pre4[0] = 0;
-  for (int k = 0; k < nr; ++k) {
-    if (beg[k] % 4 || (k < nr - 1 && n[k] % 4)) throw std::runtime_error("adam_apply_ranges: unaligned range");
-    r.beg4[k] = beg[k] / 4;
-    r.pre4[k + 1] = r.pre4[k] + n[k] / 4;
-  }
-  r.tail_beg = beg[nr - 1] + n[nr - 1] / 4 * 4;
-  r.tail_n = n[nr - 1] % 4;
-  const int nb = blocks_for(r.pre4[nr] * 4, 4);
+  int nb = 0;
+  const AdamRanges r = make_adam_ranges("adam_apply_ranges", nr, beg, n, &nb);
   if (a.sched.kind == LR_CONSTANT) adam_ranges_kernel<<<nb, kOptThreads, 0, s>>>(adam_const(a), r);
   else adam_ranges_sched(a, r, nb, s);
 }

@@ -65,4 +65,22 @@ __device__ __forceinline__ float base_lr(const SgdArgs& a) {
   return lr_at(a.sched, (a.step ? *a.step : 0) + a.t_offset - 1);
 }
 
+// The kernels' view of their argument: the struct itself, or the one a clip wrapper holds
+// (AdamClipArgs / SgdClipArgs, tfd_kernels.h). clip_load is the wrapper's clip factor, {norm, scale}[1]
+// of grad_norm.hip read from the device once per thread -- for a bare struct an empty tag, so that the
+// unclipped instantiations' gradient multiplier is a.grad_scale where it is used, as it always was.
+struct NoClip {};
+template <class A>
+__device__ __forceinline__ const A& optim_args(const A& a) { return a; }
+__device__ __forceinline__ const AdamArgs& optim_args(const AdamClipArgs& k) { return k.a; }
+__device__ __forceinline__ const SgdArgs& optim_args(const SgdClipArgs& k) { return k.a; }
+template <class A>
+__device__ __forceinline__ NoClip clip_load(const A&) { return NoClip{}; }
+__device__ __forceinline__ float clip_load(const AdamClipArgs& k) { return *k.gscale; }
+__device__ __forceinline__ float clip_load(const SgdClipArgs& k) { return *k.gscale; }
+template <class A>
+__device__ __forceinline__ float grad_mul(const A& a, NoClip) { return a.grad_scale; }
+template <class A>
+__device__ __forceinline__ float grad_mul(const A& a, float clip) { return a.grad_scale * clip; }
+
 }  // namespace tfd

@@ -2,9 +2,14 @@
 // templates over their argument struct. Two .hip files instantiate them: optim.hip with the
 // constant-rate views (optim_const.h: the default path, the kernels as they were before schedules)
 // and optim_sched.hip with AdamArgs / SgdArgs (the LrSchedule evaluated from the device step counter
-// where t is consumed). Separate code objects on purpose: see mnist_tail.h.
+// where t is consumed). A third, optim_clip.hip, takes them over AdamClipArgs / SgdClipArgs: the same
+// kernels with the gradient multiplier grad_scale * *gscale, the clip factor of global-norm clipping
+// read from the device (grad_norm.hip). Separate code objects on purpose: see mnist_tail.h.
 #pragma once
 #include <math.h>
+
+#include <stdexcept>
+#include <string>
 
 #include "common.h"
 #include "optim_const.h"
@@ -42,9 +47,9 @@ __device__ __forceinline__ AdamItem adam_load4(const A& a, int64_t i) {
   }
   return x;
 }
-template <class A>
-__device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, float lr_t, float c1, float c2) {
-  const f32x4 g = x.g * a.grad_scale;
+template <class A, class C>
+__device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, C clip, float lr_t, float c1, float c2) {
+  const f32x4 g = x.g * grad_mul(a, clip);
   f32x4 p = x.p, m = x.m, v = x.v;
   m = m + (g - m) * c1;
   v = v + (g * g - v) * c2;
@@ -58,8 +63,12 @@ __device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, f
 // The optimizer kernels are templates over their argument struct: the constant-rate view (AdamConst
 // / SgdConst, optim_const.h: the default path, as it was before schedules) or the struct with the
 // LrSchedule, evaluated from the step counter where t is consumed. The launchers pick by the kind.
-template <class A>
-__global__ __launch_bounds__(kOptThreads) void adam_kernel(A a) {
+// K is that struct or its clip wrapper: optim_args(k) is the struct, clip_load(k) the wrapper's device
+// clip factor (nothing for the bare struct) and grad_mul(a, clip) the gradient's multiplier, grad_scale
+// times the factor if there is one (optim_const.h).
+template <class K>
+__global__ __launch_bounds__(kOptThreads) void adam_kernel(K k) {
+  const auto& a = optim_args(k);
   // the first item's operands are loaded before t (a dependent load of the step counter) is awaited
   const int64_t n4 = a.n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
@@ -67,16 +76,17 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(A a) {
   AdamItem x{};
   if (i0 < n4) x = adam_load4(a, i0);
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
+  const auto clip = clip_load(k);  // a load like t: issued here, awaited with it
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
   const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
   for (int64_t i = i0; i < n4; i += stride) {
     if (i != i0) x = adam_load4(a, i);
-    adam_apply4(a, i, x, lr_t, c1, c2);
+    adam_apply4(a, i, x, clip, lr_t, c1, c2);
   }
   // scalar tail (n % 4)
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
-    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale;
+    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * grad_mul(a, clip);
     float m = a.m[i] + (g - a.m[i]) * c1;
     float v = a.v[i] + (g * g - a.v[i]) * c2;
     const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
@@ -94,8 +104,9 @@ struct AdamRanges {
 namespace {
 // same per-element math as adam_kernel, over a table of ranges (the logical float4 index is mapped
 // to its range by the prefix sums)
-template <class A>
-__global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(A a, AdamRanges r) {
+template <class K>
+__global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(K k, AdamRanges r) {
+  const auto& a = optim_args(k);
   // the first item's operands are loaded before t (a dependent load of the step counter) is awaited:
   // for the small conv + output-layer launch of the DP step that is one memory round trip of its ~3
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
@@ -107,17 +118,18 @@ __global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(A a, AdamRange
   AdamItem x{};
   if (i < r.pre4[r.nr]) x = adam_load4(a, phys(i));
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
+  const auto clip = clip_load(k);
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
   const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
   for (; i < r.pre4[r.nr]; i += stride) {
     const int64_t pi = phys(i);
     if (i != (int64_t)blockIdx.x * kOptThreads + threadIdx.x) x = adam_load4(a, pi);
-    adam_apply4(a, pi, x, lr_t, c1, c2);
+    adam_apply4(a, pi, x, clip, lr_t, c1, c2);
   }
   if (blockIdx.x == 0 && threadIdx.x < r.tail_n) {
     const int64_t i = r.tail_beg + threadIdx.x;
-    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale;
+    const float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * grad_mul(a, clip);
     const float m = a.m[i] + (g - a.m[i]) * c1;
     const float v = a.v[i] + (g * g - a.v[i]) * c2;
     const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
@@ -128,12 +140,14 @@ __global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(A a, AdamRange
 
 // GradientDescent / Momentum (TF ApplyMomentum: accum = accum*mu + g; p -= lr*accum,
 // nesterov: p -= lr*(g + mu*accum)); optional decoupled-from-nothing L2 weight decay folded in g.
-template <class A>  // SgdConst or SgdArgs
-__global__ __launch_bounds__(kOptThreads) void sgd_kernel(A a) {
+template <class K>  // SgdConst, SgdArgs or SgdClipArgs
+__global__ __launch_bounds__(kOptThreads) void sgd_kernel(K k) {
+  const auto& a = optim_args(k);
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
   const float lr = base_lr(a);
+  const auto clip = clip_load(k);
   for (int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
-    float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * a.grad_scale + a.weight_decay * a.p[i];
+    float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * grad_mul(a, clip) + a.weight_decay * a.p[i];
     float p = a.p[i];
     if (a.mom) {
       const float acc = a.mom[i] * a.momentum + g;
@@ -150,6 +164,23 @@ __global__ __launch_bounds__(kOptThreads) void sgd_kernel(A a) {
 inline int blocks_for(int64_t n, int per_thread) {
   const int64_t b = (n / per_thread + kOptThreads - 1) / kOptThreads;
   return (int)(b < 1 ? 1 : (b > kOptMaxBlocks ? kOptMaxBlocks : b));
+}
+
+// the range table of adam_ranges_kernel from element ranges [beg, beg + n); *blocks: its grid
+inline AdamRanges make_adam_ranges(const char* who, int nr, const int64_t* beg, const int64_t* n, int* blocks) {
+  if (nr < 1 || nr > 3) throw std::runtime_error(std::string(who) + ": 1..3 ranges");
+  AdamRanges r{};
+  r.nr = nr;
+  r.pre4[0] = 0;
+  for (int k = 0; k < nr; ++k) {
+    if (beg[k] % 4 || (k < nr - 1 && n[k] % 4)) throw std::runtime_error(std::string(who) + ": unaligned range");
+    r.beg4[k] = beg[k] / 4;
+    r.pre4[k + 1] = r.pre4[k] + n[k] / 4;
+  }
+  r.tail_beg = beg[nr - 1] + n[nr - 1] / 4 * 4;
+  r.tail_n = n[nr - 1] % 4;
+  *blocks = blocks_for(r.pre4[nr] * 4, 4);
+  return r;
 }
 
 }  // namespace

@@ -45,6 +45,9 @@ class MnistEngine : public torch::CustomClassHolder {
     gbf_ = at::zeros({TOTAL}, bf);
     step_ = at::zeros({1}, i64);
     tnext_ = at::zeros({1}, i64);
+    gnorm_ = at::zeros({2}, f32);  // {norm, scale} of the last clipped step (set_clip_norm)
+    gnorm_[1] = 1.0;
+    gpart_ = at::zeros({kGradNormMaxBlocks}, f32);
     fc1_splits_ = mnist_fc1_splits((int)B_);
     wg2_splits_ = mnist_wg2_splits((int)B_);
     p1_ = at::empty({B_, P1H, P1H, C1}, bf);
@@ -152,6 +155,17 @@ class MnistEngine : public torch::CustomClassHolder {
   }
   // lr the update from global_step = s uses (host evaluation of the same function)
   double lr_at_step(int64_t s) const { return (double)lr_at(sched_, s); }
+  // tf.clip_by_global_norm between the gradients and the optimizer, on the device: every step takes
+  // norm = ||averaged gradient||_2 (of the buffer the optimizer reads: fp32 grads(), or grads_bf16()
+  // when DP all-reduces bf16) and multiplies the gradient by scale = c / max(norm, c), exactly 1 while
+  // norm <= c. Non-finite norms get no special handling: inf gives scale 0; a NaN norm leaves scale at 1
+  // and the NaN gradients propagate as they do without clipping. c <= 0 turns clipping off (the
+  // default: the step is then launch for launch what it was). Like every optimizer setting it is baked
+  // into graphs captured before the call: capture again.
+  void set_clip_norm(double c) { clip_norm_ = c > 0 ? c : 0.0; }
+  double clip_norm() const { return clip_norm_; }
+  // {norm, scale} of the last clipped step, on the device ({0, 1} before the first)
+  at::Tensor grad_norm() { return gnorm_; }
   void set_comm(c10::intrusive_ptr<RcclComm> comm, bool bf16_grads) {
     comm_ = comm;
     bf16_comm_ = bf16_grads && !fp32_;
@@ -339,6 +353,10 @@ class MnistEngine : public torch::CustomClassHolder {
     // checked before anything is launched: the sharded schedules read the bf16 shadow, which the
     // fp32 step leaves stale
     TORCH_CHECK(!(zero_ && fp32_), "ZeRO-1 is a bf16-path option: set_zero(False) or set_dtype('bf16')");
+    // a sharded gradient has no global norm without a scalar collective inside the graph
+    TORCH_CHECK(!(clip_norm_ > 0 && (zero_ || sfb_active())), "set_clip_norm conflicts with ",
+                zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
+                ": the global norm needs the whole aggregated gradient on every rank; use the all-reduce schedule");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -347,6 +365,10 @@ class MnistEngine : public torch::CustomClassHolder {
     const bool dp = this->dp();
     timed_ = timing_;
     timed_dp_ = timing_ && dp;
+    if (clip_norm_ > 0) {
+      train_step_clip(dp);
+      return;
+    }
     if (fp32_) {
       train_step_f32(dp);
       return;
@@ -605,6 +627,92 @@ class MnistEngine : public torch::CustomClassHolder {
       hand_off(comm_stream_, ev_done_, s, "f32:opt<-ar");
     }
     apply_optimizer_range(0, TOTAL, 1.0 / (double)world(), 0, s);
+    mark(P_OPT, s);
+  }
+
+  // Step with global-norm clipping (set_clip_norm): one serial schedule for both dtypes, the shape of
+  // the unfused one-GPU step --
+  //   s: forward -> backward a -> backward b -> conv-slab reduce (step bump) -> [DP: wait c]
+  //      -> norm stage 1 -> norm stage 2 -> ONE optimizer over [0, TOTAL), t = global_step
+  //   c (DP): [wait fc bwd] all-reduce A -> [wait slab reduce] all-reduce B  (fp32 dtype: one bucket)
+  // The norm is taken of the aggregated gradient, in the buffer the optimizer reads (gbf_ with a bf16
+  // wire), so N ranks at batch B stay equal to one at N*B. The fused one-GPU tail cannot host the clip:
+  // its conv gradients are summed inside the optimizer kernel, so they do not exist when the norm is
+  // needed; and the deferred fc-region optimizer of train_step_dp would need the norm before the conv
+  // gradients exist.
+  void train_step_clip(bool dp) {
+    hipStream_t s = stream();
+    const double scale = 1.0 / (double)world();
+    const bool bf = bf16_comm_ && dp;
+    int64_t* step = (int64_t*)step_.data_ptr();
+    if (pending_opt_a_) {  // an unclipped DP graph left its fc-region optimizer running
+      wait(s, ev_opt_a_, "fc_fwd<-opt_fc");
+      pending_opt_a_ = false;
+    }
+    mark(P_START, s);
+    MnistStepArgs a = args();
+    if (fp32_) {
+      MnistF32Args f = args_f32();
+      mnist_f32_forward(f, true, s);
+      tag("fwd", s);
+      mark(P_FWD, s);
+      mnist_f32_backward(f, s);
+      tag("bwd", s);
+      mark(P_BFC, s);
+      a.wg2_slab = f.wg2_slab;
+      a.wg2_splits = f.wg2_splits;
+      a.xpre = nullptr;  // as train_step_f32: no prefetch gather
+      a.step_bump = step;
+      mnist_conv_grad_reduce(a, s);
+      tag("slab_reduce", s);
+      mark(P_BCONV, s);
+      if (dp) {
+        hand_off(s, ev_b_, comm_stream_, "ar<-slab_reduce");
+        mark(P_CA0, comm_stream_);
+        reduce_bucket(0, TOTAL, false);
+        tag("ar", comm_stream_);
+        mark(P_CA1, comm_stream_);
+        mark(P_CB0, comm_stream_);
+        mark(P_CB1, comm_stream_);
+        hand_off(comm_stream_, ev_done_, s, "grad_norm<-ar");
+      }
+    } else {
+      if (dp) set_dp_outputs(a, bf);
+      else a.step_bump = step;
+      mnist_forward_conv(a, s);
+      tag("conv_fwd", s);
+      mnist_forward_fc(a, true, s);
+      tag("fc_fwd", s);
+      mark(P_FWD, s);
+      mnist_backward_a(a, s, 0);
+      tag("fc_bwd", s);
+      mark(P_BFC, s);
+      if (dp) {
+        hand_off(s, ev_a_, comm_stream_, "ar_fc<-fc_bwd");
+        mark(P_CA0, comm_stream_);
+        reduce_bucket(BUCKET_SPLIT, TOTAL, bf);
+        tag("ar_fc", comm_stream_);
+        mark(P_CA1, comm_stream_);
+      }
+      mnist_backward_b(a, s);
+      tag("conv_bwd", s);
+      mnist_conv_grad_reduce(a, s);
+      tag("slab_reduce", s);
+      if (dp) {
+        all_reduce_conv(s, bf);  // behind bucket A's on the comm stream: ev_done_ covers both
+        wait(s, ev_done_, "grad_norm<-ar_conv");
+      } else {
+        mark(P_BCONV, s);
+      }
+    }
+    float* pair = (float*)gnorm_.data_ptr();
+    float* part = (float*)gpart_.data_ptr();
+    grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
+    grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
+    tag("grad_norm", s);
+    if (opt_ == 0) adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+    else sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+    tag("opt", s);
     mark(P_OPT, s);
   }
 
@@ -1137,6 +1245,9 @@ class MnistEngine : public torch::CustomClassHolder {
   // one GPU + Adam: the optimizer kernel also reduces the conv gradient slabs and bumps the step
   bool fuse_tail_ = true;
   bool local_bf16_grads_ = false;
+  // global-norm clipping (set_clip_norm): 0 = off; {norm, scale} and stage 1's per-block partials
+  double clip_norm_ = 0.0;
+  at::Tensor gnorm_, gpart_;
   std::map<std::string, hipGraphExec_t> graphs_;
   // capture_topology: nodes added by each tagged operation (label@step -> node handles)
   bool topo_ = false;
@@ -1191,6 +1302,9 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("set_momentum", &MnistEngine::set_momentum)
       .def("set_lr_schedule", &MnistEngine::set_lr_schedule)
       .def("lr_at_step", &MnistEngine::lr_at_step)
+      .def("set_clip_norm", &MnistEngine::set_clip_norm)
+      .def("clip_norm", &MnistEngine::clip_norm)
+      .def("grad_norm", &MnistEngine::grad_norm)
       .def("set_comm", &MnistEngine::set_comm)
       .def("set_ipc", &MnistEngine::set_ipc)
       .def("set_ipc_gather", &MnistEngine::set_ipc_gather)

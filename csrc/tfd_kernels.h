@@ -158,6 +158,23 @@ struct SgdArgs {
   const int64_t* step;         // read only when the schedule is not constant; null: 0
   int t_offset;
 };
+// Global-norm clipping: the same kernels with the gradient multiplier grad_scale * *gscale, gscale
+// the clip factor on the device ({norm, scale}[1] of grad_norm_finish). Wrappers, so AdamArgs /
+// SgdArgs and their constant-rate views keep their layout (optim_clip.hip holds the instantiations).
+struct AdamClipArgs { AdamArgs a; const float* gscale; };
+struct SgdClipArgs { SgdArgs a; const float* gscale; };
+void adam_apply_clip(const AdamClipArgs& a, hipStream_t s);
+void adam_ranges_clip(const AdamClipArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s);
+void sgd_apply_clip(const SgdClipArgs& a, hipStream_t s);
+// Global gradient norm (grad_norm.hip), two plain launches, bit-identical run to run:
+//   grad_sumsq: sum of squares of n fp32 (g) or n bf16 (gbf, when non-null) elements as one fp32
+//     partial per block into partials[0, grad_norm_blocks(n)) -- a fixed grid, a function of n alone;
+//   grad_norm_finish: out = {norm, scale}, norm = grad_scale * sqrt(sum of the partials in fp64),
+//     scale = clip_norm / max(norm, clip_norm) in fp32 (exactly 1 while norm <= clip_norm).
+constexpr int kGradNormMaxBlocks = 512;
+int grad_norm_blocks(int64_t n);
+void grad_sumsq(const float* g, const uint16_t* gbf, int64_t n, float* partials, hipStream_t s);
+void grad_norm_finish(const float* partials, int nb, float grad_scale, float clip_norm, float* out, hipStream_t s);
 // roofline probes: the optimizer's byte floor (Adam's 28 B/param of traffic, optional extra fp32 read
 // stream of nx4 float4) and an empty launch (tools/debug/roofline_probe.py)
 void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf, const float* x, int64_t n4, int64_t nx4,

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --clip_norm --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -51,12 +51,15 @@ def main(argv=None):
                     "reference's)")
     ap.add_argument("--host_feed", action="store_true", help="GPU: feed every batch from the host (next_batch + "
                     "H2D) instead of the device-resident split with a per-epoch device shuffle")
+    ap.add_argument("--clip_norm", type=float, default=0.0, help="tf.clip_by_global_norm on the gradient before "
+                    "Adam (GPU: norm and clip factor taken on the device inside the step graph); 0 = off")
     a = ap.parse_args(argv)
 
     # Import MNIST data (mnist_single.py:14-15)
     mnist = input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed)
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and not a.cpu) else torch.device("cpu")
-    runner = make_runner(a.batch_size, AdamOptimizer(a.learning_rate), dev, keep_prob=dropout, seed=a.seed,
+    opt = AdamOptimizer(a.learning_rate, clip_norm=a.clip_norm if a.clip_norm > 0 else None)
+    runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,
                          use_graph=not a.no_graph, dtype=a.dtype)
     runner.load_flat(M.flat_from_dict(M.init_params(a.seed)), {}, 0)  # init = initialize_all_variables()
     device_input = dev.type == "cuda" and not a.host_feed

@@ -184,6 +184,14 @@ class TorchMnistRunner(MnistRunnerBase):
     def last_loss(self) -> float:
         return float(getattr(self, "_last_loss", float("nan")))
 
+    def last_grad_norm(self) -> Tuple[float, float]:
+        """``(norm, clip scale)`` of the last step's averaged gradient (``clip_norm`` set; the flat
+        applier clips after the all-reduce), else ``(nan, 1.0)``."""
+        a = self.applier
+        if a.last_grad_norm is None:
+            return float("nan"), 1.0
+        return float(a.last_grad_norm), float(a.last_clip_scale)
+
     def set_phase_timing(self, on: bool = True) -> None:
         pass
 
@@ -230,6 +238,9 @@ class NativeMnistRunner(MnistRunnerBase):
         if is_schedule(o.learning_rate):
             # evaluated by the optimizer kernels from the device global_step (csrc/lr_schedule.h)
             self.eng.set_lr_schedule(*schedule_args(o.learning_rate))
+        if getattr(o, "clip_norm", None):
+            # norm and clip factor taken on the device inside the step graph (csrc/kernels/grad_norm.hip)
+            self.eng.set_clip_norm(float(o.clip_norm))
         self.comm = comm
         if comm is not None:
             self.eng.set_comm(comm, bf16_grads)
@@ -271,6 +282,15 @@ class NativeMnistRunner(MnistRunnerBase):
         """Mean training loss of the last step's batch (with its dropout mask)."""
         self.stream.synchronize()
         return float(self.eng.loss_rows().mean().item())
+
+    def last_grad_norm(self) -> Tuple[float, float]:
+        """``(norm, clip scale)`` of the last clipped step's averaged gradient: a host read of the
+        device pair, so call it only when something is logged. ``(nan, 1.0)`` without ``clip_norm``."""
+        if not self.eng.clip_norm() > 0:
+            return float("nan"), 1.0
+        self.stream.synchronize()
+        norm, scale = self.eng.grad_norm().tolist()
+        return float(norm), float(scale)
 
     # ---- device-resident input (reference feed: mnist_python_m.py:291-294) ----
     def set_device_dataset(self, images, labels, seed: int = 0) -> None:

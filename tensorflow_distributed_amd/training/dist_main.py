@@ -74,6 +74,9 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("lr_power", 1.0, "--lr_schedule=polynomial: power")
     f.DEFINE_float("lr_alpha", 0.0, "--lr_schedule=cosine: floor, as a fraction of --learning_rate")
     f.DEFINE_integer("lr_warmup_steps", 0, "Linear warm-up: for step < this, the rate is scaled by (step + 1) / this")
+    f.DEFINE_float("clip_norm", 0.0, "tf.clip_by_global_norm on the aggregated (averaged) gradient before the "
+                   "optimizer; on GPUs the norm and the clip factor are taken on the device inside the step "
+                   "graph. 0 = off. Synchronous all-reduce training of --model mnist_cnn only")
     f.DEFINE_boolean("sync_replicas", True, "Use the sync_replicas (synchronized replicas) mode, "
                      "wherein the parameter updates from workers are aggregated before applied to "
                      "avoid stale gradients")
@@ -176,11 +179,33 @@ def _make_optimizer():
     from .optimizers import AdamOptimizer, GradientDescentOptimizer, MomentumOptimizer
 
     lr = _make_learning_rate()
+    clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
     if FLAGS.optimizer == "sgd":
-        return GradientDescentOptimizer(lr)
+        return GradientDescentOptimizer(lr, clip_norm=clip)
     if FLAGS.optimizer == "momentum":
-        return MomentumOptimizer(lr, FLAGS.momentum)
-    return AdamOptimizer(lr)
+        return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip)
+    return AdamOptimizer(lr, clip_norm=clip)
+
+
+def check_clip_norm_flags(num_workers: int) -> None:
+    """--clip_norm clips the aggregated gradient of synchronous all-reduce training. The combinations
+    it does not cover yet are flag errors, raised before any process group is built, not silently
+    unclipped runs; each is a follow-up."""
+    if FLAGS.clip_norm < 0:
+        raise ValueError("--clip_norm=%g: must be >= 0 (0 = off)" % FLAGS.clip_norm)
+    if not FLAGS.clip_norm > 0:
+        return
+    if not FLAGS.sync_replicas:
+        raise ValueError("--clip_norm with --sync_replicas=False: the asynchronous parameter server applies each "
+                         "worker's gradient on its own, there is no aggregated gradient to clip (follow-up: "
+                         "per-push clipping on the ps)")
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("--clip_norm with backup workers (--replicas_to_aggregate=%d < %d workers): the "
+                         "accumulator paths do not clip yet (follow-up)" % (r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--clip_norm with --model %s: the ResNet runner's bucketed optimizer does not clip yet "
+                         "(follow-up)" % FLAGS.model)
 
 
 def host_identity() -> str:
@@ -398,7 +423,9 @@ def _max_over(group, v: float) -> float:
 def dp_candidates(device_type: str, dtype: str):
     """The sync DP schedules this worker device can run (parallel/schedule.py), in probe order."""
     if device_type == "cuda":
-        return list(SCH.MNIST_SCHEDULES) if dtype == "bf16" else ["allreduce"]
+        # --clip_norm: the global norm needs the whole aggregated gradient on every rank, which the
+        # SFB / ZeRO schedules never form (MnistEngine.set_clip_norm)
+        return list(SCH.MNIST_SCHEDULES) if dtype == "bf16" and not FLAGS.clip_norm > 0 else ["allreduce"]
     return list(SCH.CPU_SCHEDULES)
 
 
@@ -515,6 +542,9 @@ def _choose_schedule(server, cluster, mnist, device, is_chief):
     else:
         run_one = lambda name: _probe_cpu_schedule(name, num_workers, grp)  # noqa: E731
     log = (lambda m: print(m, file=sys.stderr, flush=True)) if is_chief else None
+    if is_chief and device.type == "cuda" and FLAGS.clip_norm > 0:
+        print("Worker %d: --clip_norm clips the all-reduced gradient: DP schedule candidates restricted to allreduce"
+              % FLAGS.task_index)
     dp_sched, dp_probe, dp_source = choose_dp_schedule(run_one, FLAGS.task_index, num_workers, device.type, grp, log)
     if is_chief:
         print("Worker %d: DP schedule %s (%s%s)" % (
@@ -574,6 +604,8 @@ def main(argv=None) -> int:
         raise ValueError("Must specify an explicit `job_name`")
     if FLAGS.task_index is None or FLAGS.task_index == "":
         raise ValueError("Must specify an explicit `task_index`")
+
+    check_clip_norm_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -705,6 +737,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                        images_per_sec=FLAGS.batch_size * (num_workers if sync else 1) / max(now - t0, 1e-9))
             if gsync.logs_lr:
                 rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
+            if FLAGS.clip_norm > 0:
+                rec["grad_norm"], rec["clip_scale"] = runner.last_grad_norm()
             if phase_timing:
                 ph = runner.phase_times()
                 rec.update(ph)

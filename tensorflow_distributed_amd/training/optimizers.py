@@ -23,6 +23,11 @@ of every optimizer config is a float or one of the schedule dataclasses below. A
 function of ``global_step`` *before* the update (Adam's ``t - 1``), which is what TF's graph reads.
 :func:`lr_at` is the fp64 definition; the GPU kernels evaluate the same formulas in fp32 from the
 device step counter (``csrc/lr_schedule.h``), so a captured step graph follows the schedule.
+
+Global-norm gradient clipping (``tf.clip_by_global_norm`` between ``compute_gradients`` and
+``apply_gradients``): ``clip_norm`` on every optimizer config. :func:`clip_by_global_norm` is the fp64
+definition; the GPU engine takes the norm and the factor on the device inside the step graph
+(``csrc/kernels/grad_norm.hip``, ``optim_clip.hip``).
 """
 from __future__ import annotations
 
@@ -181,6 +186,7 @@ class AdamOptimizer:
     epsilon: float = 1e-8
     name: str = "Adam"
     kind: str = field(default="adam", init=False)
+    clip_norm: Optional[float] = None
 
 
 @dataclass
@@ -188,6 +194,7 @@ class GradientDescentOptimizer:
     learning_rate: LearningRate = 0.01
     name: str = "GradientDescent"
     kind: str = field(default="sgd", init=False)
+    clip_norm: Optional[float] = None
 
 
 @dataclass
@@ -197,6 +204,7 @@ class MomentumOptimizer:
     use_nesterov: bool = False
     name: str = "Momentum"
     kind: str = field(default="momentum", init=False)
+    clip_norm: Optional[float] = None
 
 
 @dataclass
@@ -220,6 +228,24 @@ class SyncReplicasOptimizer:
             self.replicas_to_aggregate < self.total_num_replicas
 
 
+def clip_by_global_norm(g: torch.Tensor, clip_norm: float, scale: float = 1.0) -> Tuple[float, float]:
+    """``(factor, norm)`` of ``tf.clip_by_global_norm`` over the flat gradient ``g``, in fp64.
+
+    ``norm = scale * sqrt(sum g_i^2)`` is the norm of the gradient the optimizer consumes (``scale`` is
+    the 1/N of a sum-all-reduce); the optimizer's gradient is ``g * factor`` with
+    ``factor = scale * clip_norm / max(norm, clip_norm)``. The clip part is *exactly* 1.0 whenever
+    ``norm <= clip_norm`` (TF's ``clip_norm * min(1/norm, 1/clip_norm)`` equals it up to rounding), so
+    an inactive clip changes no bit. Non-finite norms get no special handling: an ``inf`` norm gives
+    factor 0; a NaN norm fails the comparison, leaves the clip part at 1, and the NaN gradient
+    elements propagate as they do without clipping. The device kernels do the same in fp32.
+    """
+    c = float(clip_norm)
+    if not c > 0:
+        raise ValueError(f"clip_norm must be > 0, got {clip_norm!r}")
+    norm = float(scale) * math.sqrt(float(g.detach().to(torch.float64).pow(2).sum().item()))
+    return float(scale) * (c / (norm if norm > c else c)), norm
+
+
 def base_optimizer(opt):
     return opt.opt if isinstance(opt, SyncReplicasOptimizer) else opt
 
@@ -240,10 +266,16 @@ class FlatApplier:
         z = lambda: torch.zeros(numel, dtype=torch.float32, device=device)  # noqa: E731
         self.m = z() if k in ("adam", "momentum") else None
         self.v = z() if k == "adam" else None
+        self.last_grad_norm: Optional[float] = None  # norm / clip part of the last clipped apply()
+        self.last_clip_scale: Optional[float] = None
 
     @torch.no_grad()
     def apply(self, p: torch.Tensor, g: torch.Tensor, scale: float = 1.0) -> None:
         o = self.opt
+        if getattr(o, "clip_norm", None):
+            factor, self.last_grad_norm = clip_by_global_norm(g, o.clip_norm, scale)
+            self.last_clip_scale = factor / scale
+            scale = factor
         g = g if scale == 1.0 else g * scale
         lr = lr_at(o.learning_rate, self.t)  # global_step before this update
         self.t += 1

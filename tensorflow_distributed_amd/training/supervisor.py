@@ -106,6 +106,9 @@ class Supervisor:
         lr = self._learning_rate(global_step)
         if lr is not None:
             vals.setdefault("learning_rate", lr)
+        norm = self._global_norm()
+        if norm is not None:
+            vals.setdefault("global_norm", norm)
         if now > t0:
             vals["global_step/sec"] = (global_step - s0) / (now - t0)
         self.writer.add_scalars(vals, global_step)
@@ -120,6 +123,15 @@ class Supervisor:
         if lr is None:
             lr = getattr(self.runner, "learning_rate", None)
         return None if lr is None else lr_at(lr, global_step)
+
+    def _global_norm(self) -> Optional[float]:
+        """Norm of the last step's aggregated gradient when the runner clips by global norm (a host
+        read of the device pair on GPUs: only here, when a summary is written)."""
+        if not getattr(getattr(self.runner, "opt", None), "clip_norm", None):
+            return None
+        read = getattr(self.runner, "last_grad_norm", None)
+        norm = float(read()[0]) if read is not None else float("nan")
+        return None if norm != norm else norm  # NaN: no clipped step yet
 
     def save(self, global_step: Optional[int] = None) -> Optional[str]:
         if not (self.is_chief and self.logdir):
