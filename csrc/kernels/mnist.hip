@@ -23,6 +23,7 @@
 
 #include "../gemm.h"
 #include "../gemm256.h"  // kc_slot, make_rsrc, DenseSrc (the fc1 dX DMA ring)
+#include "../launch_check.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
 #include "../mnist_tail.h"
@@ -532,6 +533,13 @@ __global__ __launch_bounds__(256) void head_kernel(MnistStepArgs a, int train) {
 // One 256-thread block owns 64 rows m (thread = row m0 + (t & 63), batch quarter t >> 6); dlogits
 // [B][10] staged in LDS; the 4 batch quarters are summed through LDS (deterministic).
 constexpr int OUTG_ROWS = 64;
+// dynamic LDS of an output-layer block: dlogits [B][10] + the batch quarters' partials [4][64][10].
+// It is the one launch whose LDS grows with the batch, so it sets the largest batch the step can run
+// (mnist_max_batch): 160 KiB of LDS per workgroup on gfx950.
+constexpr int LDS_PER_BLOCK = 160 * 1024;
+constexpr int outg_smem(int B) { return (B * NCLS + 4 * OUTG_ROWS * NCLS) * 4; }
+constexpr int OUTG_MAX_B = (LDS_PER_BLOCK / 4 - 4 * OUTG_ROWS * NCLS) / NCLS;  // 3840
+static_assert(outg_smem(OUTG_MAX_B) <= LDS_PER_BLOCK && outg_smem(OUTG_MAX_B + 1) > LDS_PER_BLOCK, "largest batch");
 constexpr int OUTG_BLOCKS = (HID + 1 + OUTG_ROWS - 1) / OUTG_ROWS;  // 17 (last block: bias row)
 constexpr int OUTG_LB = 16; // hd loads batched per thread (a one-at-a-time loop was a 32-deep latency chain)
 __device__ __forceinline__ void out_grad_block(const MnistStepArgs& a, int blk, float* smem) {
@@ -1423,13 +1431,14 @@ template <auto K>
 inline void set_smem(int bytes) {  // raise the kernel's dynamic-LDS limit to the largest size asked so far
   static int limit = 64 * 1024;
   if (bytes > limit) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     limit = bytes;
   }
 }
 
 }  // namespace
 
+int mnist_max_batch() { return std::min(OUTG_MAX_B, mnist_f32_max_batch()); }
 int mnist_fc1_splits(int B) { (void)B; return FC1_SPLITS; }
 int mnist_wg2_splits(int B) { return (B + C2WL_IMG - 1) / C2WL_IMG; }  // one slab per image group
 
@@ -1440,7 +1449,7 @@ void mnist_forward(const MnistStepArgs& a, bool train, hipStream_t s) {
 
 void mnist_forward_conv(const MnistStepArgs& a, hipStream_t s) {
   set_smem<conv12_fwd_lds>(C12_SMEM);
-  conv12_fwd_lds<<<2 * a.B, 512, C12_SMEM, s>>>(a);
+  TFD_LAUNCH(conv12_fwd_lds<<<2 * a.B, 512, C12_SMEM, s>>>(a));
 }
 
 void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
@@ -1451,9 +1460,9 @@ void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
     set_smem<fc1_fwd>(sm);
     const int kper = (FEAT + a.fc1_splits - 1) / a.fc1_splits;
     dim3 g(HID / FC1_BN, (B + FC1_BM - 1) / FC1_BM, a.fc1_splits);
-    fc1_fwd<<<g, 256, sm, s>>>(a, kper);
+    TFD_LAUNCH(fc1_fwd<<<g, 256, sm, s>>>(a, kper));
   }
-  head_kernel<<<B, 256, 0, s>>>(a, train ? 1 : 0);
+  TFD_LAUNCH(head_kernel<<<B, 256, 0, s>>>(a, train ? 1 : 0));
 }
 
 void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {
@@ -1462,12 +1471,12 @@ void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {
   static_assert(sm_dw >= FDW_BM * FDW_PITCH * 4, "fc1 dW staging image fits the GEMM's LDS");
   constexpr int sm_dx = GemmSmem<FDX_BM, FDX_BN, FDX_BK, DenseLoaderX<true>, DenseLoaderX<true>>::BYTES;
   static_assert(sm_dx >= FDX_BM * (FDX_BN + 4) * 4, "fc1 dX staging image fits the GEMM's LDS");
-  const int sm_og = (B * NCLS + 4 * OUTG_ROWS * NCLS) * 4;
-  const int sm = std::max(std::max(sm_dw, part == 2 ? sm_dx : FDXD_SMEM), sm_og);
+  if (B > OUTG_MAX_B) throw std::runtime_error("mnist_backward_a: batch above mnist_max_batch()");
+  const int sm = std::max(std::max(sm_dw, part == 2 ? sm_dx : FDXD_SMEM), outg_smem(B));
   set_smem<fc1_bwd>(sm);
   const int n_dx = FDX_GX * ((B + FDX_BM - 1) / FDX_BM);
   const int nb = part == 2 ? FDX_GX2 * ((B + FDX_BM - 1) / FDX_BM) : FDW_GX * FDW_GY + (part == 0 ? n_dx : 0) + OUTG_BLOCKS;
-  fc1_bwd<<<nb, 256, sm, s>>>(a, n_dx, part);
+  TFD_LAUNCH(fc1_bwd<<<nb, 256, sm, s>>>(a, n_dx, part));
 }
 
 void mnist_backward_b(const MnistStepArgs& a, hipStream_t s) {
@@ -1476,18 +1485,18 @@ void mnist_backward_b(const MnistStepArgs& a, hipStream_t s) {
   static_assert(C2WL_SMEM <= C2D_SMEM, "conv2_bwd_lds: the dgrad LDS size covers the wgrad blocks");
   set_smem<conv2_bwd_lds>(C2D_SMEM);
   const int nw = C2WL_NTG * a.wg2_splits;
-  conv2_bwd_lds<<<nw + 2 * a.B, C2B_NT, C2D_SMEM, s>>>(a, nw);
+  TFD_LAUNCH(conv2_bwd_lds<<<nw + 2 * a.B, C2B_NT, C2D_SMEM, s>>>(a, nw));
 }
 
 void mnist_conv_grad_reduce(const MnistStepArgs& a, hipStream_t s) {
   const bool gather = a.step_bump && a.perm && a.xpre;
   if (gather && a.t_out) {  // one launch: gather blocks read the next step from t_out
-    reduce_conv_grads<<<a.B + RED2_BLOCKS + RED1_BLOCKS, 256, 0, s>>>(a, a.B);
+    TFD_LAUNCH(reduce_conv_grads<<<a.B + RED2_BLOCKS + RED1_BLOCKS, 256, 0, s>>>(a, a.B));
     return;
   }
   // the next step's batch first (this kernel bumps the step; the gather reads it unbumped)
-  if (gather) gather_next_kernel<<<a.B, 256, 0, s>>>(a);
-  reduce_conv_grads<<<RED2_BLOCKS + RED1_BLOCKS, 256, 0, s>>>(a, 0);
+  if (gather) TFD_LAUNCH(gather_next_kernel<<<a.B, 256, 0, s>>>(a));
+  TFD_LAUNCH(reduce_conv_grads<<<RED2_BLOCKS + RED1_BLOCKS, 256, 0, s>>>(a, 0));
 }
 
 void mnist_adam_fused(const MnistStepArgs& a, const MnistAdamArgs& o, hipStream_t s, bool fc_region) {
@@ -1516,7 +1525,7 @@ void mnist_fc_grad_sfb(const MnistStepArgs& a, hipStream_t s, bool with_reduce) 
     gb = (a.step_bump && a.perm && a.xpre) ? a.B : 0;
     nlead = gb + RED2_BLOCKS + RED1_BLOCKS;
   }
-  fc_grad_sfb<<<nlead + OUTS_BLOCKS + FDW_GX * nby, 256, sm, s>>>(a, gb, nlead);
+  TFD_LAUNCH(fc_grad_sfb<<<nlead + OUTS_BLOCKS + FDW_GX * nby, 256, sm, s>>>(a, gb, nlead));
 }
 
 void mnist_sfb_tile_rows(int row0, int row1, int* by_lo, int* by_hi) {

@@ -15,6 +15,7 @@
 
 #include "../gemm.h"  // buf_ld
 #include "../gemm_f32.h"
+#include "../launch_check.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
 
@@ -347,6 +348,12 @@ __global__ __launch_bounds__(256) void f32_head(MnistF32Args a, int train) {
 
 // ---------------- K8: output layer dW/db [1025][10] = [Hd;1]^T dlogits ----------------
 constexpr int F_OUTG_ROWS = 64;
+// dynamic LDS of an output-layer block (dlogits [B][10] + [4][64][10] partials): the one launch whose
+// LDS grows with the batch, so it bounds the batch (mnist_f32_max_batch; 160 KiB per workgroup)
+constexpr int F_LDS_PER_BLOCK = 160 * 1024;
+constexpr int f_outg_smem(int B) { return (B * NCLS + 4 * F_OUTG_ROWS * NCLS) * 4; }
+constexpr int F_OUTG_MAX_B = (F_LDS_PER_BLOCK / 4 - 4 * F_OUTG_ROWS * NCLS) / NCLS;  // 3840
+static_assert(f_outg_smem(F_OUTG_MAX_B) <= F_LDS_PER_BLOCK && f_outg_smem(F_OUTG_MAX_B + 1) > F_LDS_PER_BLOCK, "largest batch");
 constexpr int F_OUTG_BLOCKS = (HID + 1 + F_OUTG_ROWS - 1) / F_OUTG_ROWS;  // 17
 __device__ __forceinline__ void f32_out_grad_block(const MnistF32Args& a, int blk, float* smem) {
   float* dl = smem;                 // [B][10]
@@ -778,28 +785,30 @@ __global__ __launch_bounds__(512) void f32_conv2_bwd_lds(MnistF32Args a, int nw)
 }
 
 template <auto K>
-inline void set_smem_f(int bytes) {
-  static bool done = false;
-  if (!done && bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  done = true;
+inline void set_smem_f(int bytes) {  // raise the kernel's dynamic-LDS limit to the largest size asked so far
+  static int limit = 64 * 1024;
+  if (bytes > limit) {
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    limit = bytes;
+  }
 }
 
 }  // namespace
 
+int mnist_f32_max_batch() { return F_OUTG_MAX_B; }
 int mnist_f32_fc1_splits() { return F_FC1_SPLITS; }
 int mnist_f32_wg2_splits(int B) { return (B + F2W_IMG - 1) / F2W_IMG; }  // one slab per image pair
 
 void mnist_f32_forward(const MnistF32Args& a, bool train, hipStream_t s) {
   const int B = a.B;
   set_smem_f<f32_conv12_fwd_lds>(F2F_SMEM);
-  f32_conv12_fwd_lds<<<2 * B, 512, F2F_SMEM, s>>>(a);
+  TFD_LAUNCH(f32_conv12_fwd_lds<<<2 * B, 512, F2F_SMEM, s>>>(a));
   {
     constexpr int sm = GemmSmemF<64, 64, F_BK, DenseLoaderF<true>, DenseLoaderF<false>>::BYTES;
     set_smem_f<f32_fc1_fwd>(sm);
-    f32_fc1_fwd<<<dim3(HID / 64, (B + 63) / 64, F_FC1_SPLITS), 256, sm, s>>>(a);
+    TFD_LAUNCH(f32_fc1_fwd<<<dim3(HID / 64, (B + 63) / 64, F_FC1_SPLITS), 256, sm, s>>>(a));
   }
-  f32_head<<<B, 256, 0, s>>>(a, train ? 1 : 0);
+  TFD_LAUNCH(f32_head<<<B, 256, 0, s>>>(a, train ? 1 : 0));
 }
 
 void mnist_f32_backward(const MnistF32Args& a, hipStream_t s) {
@@ -807,15 +816,15 @@ void mnist_f32_backward(const MnistF32Args& a, hipStream_t s) {
   {
     constexpr int sm_dw = GemmSmemF<64, 64, F_BK, OnesRowMCF, DenseLoaderF<false>>::BYTES;
     constexpr int sm_dx = GemmSmemF<32, 64, F_DX_BK, DenseLoaderF<true>, DenseLoaderF<true>>::BYTES;
-    const int sm_og = (B * NCLS + 4 * F_OUTG_ROWS * NCLS) * 4;
-    const int sm = std::max(std::max(sm_dw, sm_dx), sm_og);
+    if (B > F_OUTG_MAX_B) throw std::runtime_error("mnist_f32_backward: batch above mnist_max_batch()");
+    const int sm = std::max(std::max(sm_dw, sm_dx), f_outg_smem(B));
     set_smem_f<f32_fc1_bwd>(sm);
     const int n_dx = F_DX_GX * ((B + 31) / 32);
-    f32_fc1_bwd<<<F_OUTG_BLOCKS + n_dx + F_DW_GX * F_DW_GY, 256, sm, s>>>(a, n_dx);
+    TFD_LAUNCH(f32_fc1_bwd<<<F_OUTG_BLOCKS + n_dx + F_DW_GX * F_DW_GY, 256, sm, s>>>(a, n_dx));
   }
   set_smem_f<f32_conv2_bwd_lds>(F2D_SMEM_T);
   const int nw = F2W_NTG * a.wg2_splits;
-  f32_conv2_bwd_lds<<<nw + 2 * B, 512, F2D_SMEM_T, s>>>(a, nw);
+  TFD_LAUNCH(f32_conv2_bwd_lds<<<nw + 2 * B, 512, F2D_SMEM_T, s>>>(a, nw));
 }
 
 }  // namespace tfd

@@ -7,6 +7,7 @@
 // step (docs/DESIGN.md section 9).
 #pragma once
 #include "common.h"
+#include "launch_check.h"
 #include "mnist_layout.h"
 #include "optim_const.h"
 #include "tfd_kernels.h"
@@ -196,7 +197,7 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
 template <class Opt>
 inline void mnist_adam_launch(const MnistStepArgs& a, const Opt& o, hipStream_t s, bool fc_region) {
   const int gb = (a.perm && a.xpre) ? a.B : 0;
-  mnist_adam_kernel<<<gb + MAD_CONV + (fc_region ? MAD_FC_BLOCKS : 0), MAD_NT, 0, s>>>(a, o, (int)(OFF_WD1 / 4));
+  TFD_LAUNCH(mnist_adam_kernel<<<gb + MAD_CONV + (fc_region ? MAD_FC_BLOCKS : 0), MAD_NT, 0, s>>>(a, o, (int)(OFF_WD1 / 4)));
 }
 
 }  // namespace

@@ -31,7 +31,10 @@ class MnistEngine : public torch::CustomClassHolder {
  public:
   MnistEngine(int64_t batch, int64_t device, double keep_prob, int64_t seed, int64_t rank)
       : B_(batch), device_(device), keep_prob_(keep_prob), seed_((uint32_t)seed), rank_((uint32_t)rank) {
-    TORCH_CHECK(batch > 0 && batch <= 65536, "bad batch");
+    // the output-layer gradient blocks stage dlogits [B][10] in LDS: above mnist_max_batch() their
+    // launch would be refused (both precisions: set_dtype comes after construction)
+    TORCH_CHECK(batch > 0 && batch <= mnist_max_batch(), "MnistEngine: batch ", batch,
+                " outside [1, mnist_max_batch() = ", mnist_max_batch(), "]");
     auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device);
     auto bf = at::TensorOptions().dtype(at::kBFloat16).device(at::kCUDA, device);
     auto u8 = at::TensorOptions().dtype(at::kByte).device(at::kCUDA, device);
@@ -98,13 +101,30 @@ class MnistEngine : public torch::CustomClassHolder {
     return hd_;
   }
   at::Tensor pool2() {
+    if (fp32_) return f2_;
     if (sfb_active()) return sfp2_.narrow(0, rank_in_comm() * B_ * FEAT, B_ * FEAT).view({B_, FEAT});
     return p2_;
   }
-  at::Tensor pool1() { return p1_; }
+  at::Tensor pool1() { return fp32_ ? f1_ : p1_; }
+  // read-only views for the tests: each pool's argmax inside its 2x2 window (0..3, row-major; both
+  // precisions write the same buffers), the gradient at the logits (1/B folded in) and at the fc1
+  // pre-activation
+  at::Tensor pool1_argmax() { return idx1_; }
+  at::Tensor pool2_argmax() { return idx2_; }
+  at::Tensor dlogits() {
+    if (!fp32_ && sfb_active())
+      return sfdr_.narrow(0, rank_in_comm() * sfb_rs_ + 2 * B_ * HID, 2 * B_ * NCLS).view(at::kFloat).view({B_, NCLS});
+    return dlogits_;
+  }
+  at::Tensor dhidden() {
+    if (fp32_) return fdh_;
+    if (sfb_active()) return sfdr_.narrow(0, rank_in_comm() * sfb_rs_, B_ * HID).view({B_, HID});
+    return dh_;
+  }
   at::Tensor feed_x() { return xbuf_; }
   at::Tensor feed_y() { return ybuf_; }
   int64_t batch() { return B_; }
+  static int64_t max_batch() { return mnist_max_batch(); }
 
   void set_dataset(at::Tensor data, at::Tensor labels, at::Tensor perm) {
     TORCH_CHECK(data.is_cuda() && data.scalar_type() == at::kFloat && data.dim() == 2 && data.size(1) == 784,
@@ -1260,6 +1280,8 @@ class MnistEngine : public torch::CustomClassHolder {
 };
 
 TORCH_LIBRARY_FRAGMENT(tfd, m) {
+  // the largest batch an MnistEngine accepts (csrc/tfd_kernels.h)
+  m.def("mnist_max_batch() -> int", []() -> int64_t { return mnist_max_batch(); });
   m.class_<RcclComm>("RcclComm")
       .def(torch::init<at::Tensor, int64_t, int64_t, int64_t>())
       .def_static("unique_id", &RcclComm::unique_id)
@@ -1289,6 +1311,11 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("hidden", &MnistEngine::hidden)
       .def("pool1", &MnistEngine::pool1)
       .def("pool2", &MnistEngine::pool2)
+      .def("pool1_argmax", &MnistEngine::pool1_argmax)
+      .def("pool2_argmax", &MnistEngine::pool2_argmax)
+      .def("dlogits", &MnistEngine::dlogits)
+      .def("dhidden", &MnistEngine::dhidden)
+      .def_static("max_batch", &MnistEngine::max_batch)
       .def("feed_x", &MnistEngine::feed_x)
       .def("feed_y", &MnistEngine::feed_y)
       .def("batch", &MnistEngine::batch)

@@ -67,6 +67,11 @@ struct MnistStepArgs {
   int sfb_by_lo, sfb_by_hi;
 };
 
+// The largest per-rank batch the step's launches can run: the output-layer gradient blocks stage
+// dlogits [B][10] in dynamic LDS (160 KiB per workgroup). The minimum over the bf16 and fp32 paths,
+// which an engine can switch between after construction.
+int mnist_max_batch();
+int mnist_f32_max_batch();
 int mnist_fc1_splits(int B);
 int mnist_wg2_splits(int B);
 void mnist_forward(const MnistStepArgs& a, bool train, hipStream_t s);        // conv1, conv2, fc1, head

@@ -69,7 +69,7 @@ def test_forced_dp_world1_gradients_are_the_fused_gradients(cuda, mode):
     tr.close()
 
 
-@pytest.mark.parametrize("mode,B", [("rccl", 128), ("ipc", 128), ("ipc", 512)])
+@pytest.mark.parametrize("mode,B", [("rccl", 128), ("ipc", 128), ("ipc", 512), ("rccl", 37), ("ipc", 37)])
 def test_forced_dp_world1_sfb_gradients_are_the_fused_gradients(cuda, mode, B):
     """Sufficient-factor fc gradients at world 1 (gather of the own factors, GEMM over K = B):
     fc1 dW + bias are the one-GPU step's fp32 gradients rounded to bf16 bit for bit (same K order;

@@ -6,6 +6,7 @@ the native kernels store/consume bf16). Gradients come from torch autograd on th
 import pytest
 import torch
 
+import mnist_oracle as O
 from tensorflow_distributed_amd.models import mnist_cnn as M
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +73,10 @@ def test_step_grads_match_oracle(cuda, scale, B):
         if k != "loss":
             gm[k] = g[k] * 1.02
         assert k in _oracle_errors(lm, loss_ref, gm, g_ref), f"a 1.02x {k} passes the bounds"
+    # the localised check: every slice of every tensor against the fp64 oracle (tests/mnist_oracle.py)
+    got = O.collect(eng)
+    bad = O.check(got, O.oracle_step(params, x, y, "bf16", follow=got), "bf16")
+    assert not bad, bad
 
 
 def test_adam_step_and_counter(cuda):

@@ -4,6 +4,7 @@ fp32 matrix core. Gradients must match the fp32 PyTorch oracle to <= 1e-4 relati
 import pytest
 import torch
 
+import mnist_oracle as O
 from tensorflow_distributed_amd.models import mnist_cnn as M
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,10 @@ def test_fp32_step_grads_match_oracle(cuda, scale, B):
     g = M.dict_from_flat(eng.grads().cpu())
     errs = {k: _relerr(g[k].double(), p[k].grad) for k in p}
     assert max(errs.values()) < 1e-4, errs
+    # the localised check: every slice of every tensor against the fp64 oracle (tests/mnist_oracle.py)
+    got = O.collect(eng)
+    bad = O.check(got, O.oracle_step(params, x, y, "fp32", follow=got), "fp32")
+    assert not bad, bad
 
 
 def test_fp32_training_step_with_dropout_and_sgd(cuda):

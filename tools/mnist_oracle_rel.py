@@ -1,9 +1,17 @@
-"""Per-tensor relative L2 error of the fused bf16 MNIST step against the fp32 oracle that rounds to
-bf16 where the kernels do (models.mnist_cnn.conv_net(emulate_bf16=True)): the calibration behind
-the per-tensor bounds of tests/test_mnist_engine_gpu.py::test_step_grads_match_oracle (bounds set
-at about 3x the measured errors, like profiles/resnet_oracle_rel_r5.txt for ResNet).
+"""Errors of the native MNIST step against its oracles: the calibration behind the test bounds.
 
-    python tools/mnist_oracle_rel.py [--seeds 0,1,2]
+Default: per-tensor relative L2 error of the fused bf16 step against the fp32 oracle that rounds to
+bf16 where the kernels do (models.mnist_cnn.conv_net(emulate_bf16=True)): the bounds of
+tests/test_mnist_engine_gpu.py::test_step_grads_match_oracle (about 3x the measured errors, like
+profiles/resnet_oracle_rel_r5.txt for ResNet).
+
+--slices: per-slice errors (tests/mnist_oracle.py: per tap, channel, tile, image, element ...) of both
+precisions against the fp64 oracle, over the three standard configurations, the edge batches and the
+B = 37 dropout case at three seeds each, then the special-input cases of
+tests/test_mnist_kernel_edges_gpu.py (reported, not part of the bounds). The last section is the
+BOUNDS table of tests/mnist_oracle.py: 3x the worst of each class.
+
+    python tools/mnist_oracle_rel.py [--seeds 0,1,2] [--slices]
 """
 import argparse
 import os
@@ -11,7 +19,8 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 from tensorflow_distributed_amd import _native  # noqa: E402
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
@@ -49,13 +58,65 @@ def measure(scale, B, seed, dev):
     return out
 
 
+def _fmt(m):
+    by = {}
+    for (t, s), (e, i) in m.items():
+        by.setdefault(t, []).append(f"{s}={e:.2e}@{i}")
+    return by
+
+
+def slices(seeds, dev):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mnist_oracle as O
+
+    worst = {}
+
+    def run(name, dtype, params, x, y, keep=1.0, count=True, follow=True):
+        mask = M.native_dropout_mask(x.shape[0], 0, 0, 1234, keep) if keep < 1.0 else None
+        got = O.run_engine(dev, dtype, params, x, y, keep)
+        ref = O.oracle_step(params, x, y, dtype, keep, mask, follow=got if follow else None)
+        m = O.measure(got, ref)
+        for t, parts in _fmt(m).items():
+            print(f"{dtype} {name} {t}: " + " ".join(parts), flush=True)
+        if count:
+            for k, (e, _) in m.items():
+                if e > worst.get((dtype, k), (-1.0, ""))[0]:
+                    worst[(dtype, k)] = (e, name)
+
+    print("# calibration set: (scale, B) x seeds, keep 1 unless stated")
+    for dtype in ("bf16", "fp32"):
+        cases = [(s, B, 1.0) for s, B in O.STANDARD] + [(0.05, B, 1.0) for B in O.EDGE_BATCHES] + [(0.05, 37, 0.75)]
+        for scale, B, keep in cases:
+            for seed in seeds:
+                params, x, y = O.random_case(B, scale, seed)
+                run(f"scale={scale} B={B} keep={keep} seed={seed}", dtype, params, x, y, keep)
+    print("# special inputs (reported; not part of the bounds)")
+    for dtype in ("bf16", "fp32"):
+        for B in (5, 37):
+            run(f"integer B={B}", dtype, *O.integer_case(B), count=False, follow=False)
+        for B in (9, 37):
+            run(f"impulse B={B}", dtype, *O.impulse_case(B), count=False)
+        for B in (6, 3):
+            for rev in (False, True):
+                run(f"neighbours B={B} reverse={rev}", dtype, *O.neighbours_case(B, rev), count=False)
+        for lab in ("zeros", "nines", "argmin"):
+            run(f"saturated B=37 labels={lab}", dtype, *O.saturated_case(37, lab), count=False)
+    print("# bounds: 3x the worst of each class over the calibration set (dtype tensor slicing worst where bound)")
+    for (dtype, (t, s)), (e, name) in sorted(worst.items()):
+        print(f"bound {dtype} {t} {s} {e:.3e} [{name}] {3 * e:.3e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", default="0,1,2")
+    ap.add_argument("--slices", action="store_true", help="per-slice errors against the fp64 oracle")
     a = ap.parse_args()
     _native.require()
     dev = torch.device("cuda", 0)
     seeds = [int(s) for s in a.seeds.split(",")]
+    if a.slices:
+        slices(seeds, dev)
+        return
     worst = {}
     for scale, B in CONFIGS:
         for seed in seeds:
