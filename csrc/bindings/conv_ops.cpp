@@ -26,6 +26,17 @@ void check_f32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), name, ": contiguous fp32 GPU tensor");
 }
 
+// a per-channel BN vector: contiguous fp32 [C]
+void check_cvec(const at::Tensor& t, const char* name, int C) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == C, name, ": expected ", C, " elements (one per channel)");
+}
+// the BN passes give each row C / 8 threads of a 256-thread block (norm.hip row_split)
+void check_bn_channels(const at::Tensor& y, const char* op) {
+  TORCH_CHECK(y.dim() >= 1 && y.size(-1) % 8 == 0 && y.size(-1) <= 2048, op, ": C must be a multiple of 8 and <= 2048");
+  TORCH_CHECK(y.numel() < (1ll << 30), op, ": tensor too large for 32-bit buffer addressing");
+}
+
 ConvShape shape_of(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad) {
   ConvShape c;
   c.N = (int)x.size(0); c.H = (int)x.size(1); c.W = (int)x.size(2); c.C = (int)x.size(3);
@@ -306,12 +317,18 @@ std::tuple<at::Tensor, at::Tensor> bn_bwd(const at::Tensor& dout, const at::Tens
   check_bf16(y, "y", -1);
   check_f32(dgamma, "dgamma");
   check_f32(dbeta, "dbeta");
+  check_bn_channels(y, "bn_bwd");
   const int C = (int)y.size(-1);
   const int M = (int)(y.numel() / C);
-  TORCH_CHECK(y.numel() < (1ll << 30) && C % 8 == 0, "bn_bwd: C % 8 and < 2^30 elements (buffer addressing)");
+  TORCH_CHECK(dout.sizes() == y.sizes() && out.sizes() == y.sizes(), "bn_bwd: dout and out must have y's shape");
+  check_cvec(gamma, "bn_bwd gamma", C);
+  check_cvec(mean, "bn_bwd mean", C);
+  check_cvec(invstd, "bn_bwd invstd", C);
+  check_cvec(dgamma, "bn_bwd dgamma", C);
+  check_cvec(dbeta, "bn_bwd dbeta", C);
   auto dy = at::empty_like(y);
   at::Tensor dres = want_dres ? at::empty_like(y) : at::Tensor();
-  if (beta) check_f32(*beta, "beta");
+  if (beta) check_cvec(*beta, "bn_bwd beta", C);
   const uint8_t* mb = nullptr;
   if (mask.has_value()) {
     TORCH_CHECK(relu && mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
@@ -335,7 +352,12 @@ std::tuple<at::Tensor, at::Tensor> bn_bwd(const at::Tensor& dout, const at::Tens
 at::Tensor bn_infer_op(const at::Tensor& y, const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& rm,
                        const at::Tensor& rv, double eps, bool relu) {
   check_bf16(y, "y", -1);
+  check_bn_channels(y, "bn_infer");
   const int C = (int)y.size(-1);
+  check_cvec(gamma, "bn_infer gamma", C);
+  check_cvec(beta, "bn_infer beta", C);
+  check_cvec(rm, "bn_infer running_mean", C);
+  check_cvec(rv, "bn_infer running_var", C);
   auto out = at::empty_like(y);
   bn_infer(bp(y), fp(gamma), fp(beta), fp(rm), fp(rv), (float)eps, relu ? 1 : 0, bp(out), (int)(y.numel() / C), C,
            cur());
@@ -379,6 +401,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_relu_maxpool_op(
 at::Tensor maxpool2d_bwd(const at::Tensor& dy, const at::Tensor& am, at::IntArrayRef xshape, int64_t k, int64_t st,
                          int64_t pad) {
   check_bf16(dy, "dy", 4);
+  TORCH_CHECK(xshape.size() == 4 && xshape[3] % 8 == 0 && xshape[3] == dy.size(3) && xshape[0] == dy.size(0),
+              "maxpool2d_bwd: xshape [N,H,W,C] with dy's N and C, C % 8 == 0");
+  TORCH_CHECK(k >= 1 && k <= 15 && st >= 1 && pad >= 0 && dy.size(1) == (xshape[1] + 2 * pad - k) / st + 1 &&
+                  dy.size(2) == (xshape[2] + 2 * pad - k) / st + 1, "maxpool2d_bwd: dy is not the pooled shape of xshape");
+  TORCH_CHECK(am.is_cuda() && am.scalar_type() == at::kByte && am.is_contiguous() && am.sizes() == dy.sizes(),
+              "maxpool2d_bwd: argmax must be a contiguous uint8 GPU tensor of dy's shape");
   auto dx = at::empty(xshape, dy.options());
   maxpool_bwd(bp(dy), am.data_ptr<uint8_t>(), bp(dx), (int)xshape[0], (int)xshape[1], (int)xshape[2], (int)xshape[3],
               (int)k, (int)st, (int)pad, (int)dy.size(1), (int)dy.size(2), cur());
@@ -387,6 +415,8 @@ at::Tensor maxpool2d_bwd(const at::Tensor& dy, const at::Tensor& am, at::IntArra
 
 at::Tensor avgpool_fwd_op(const at::Tensor& x) {
   check_bf16(x, "x", 4);
+  TORCH_CHECK(x.size(0) > 0 && x.size(1) * x.size(2) > 0 && x.size(3) > 0 && x.numel() < (1ll << 31),
+              "avgpool_fwd: non-empty [N,H,W,C] of fewer than 2^31 elements");
   const int N = (int)x.size(0), HW = (int)(x.size(1) * x.size(2)), C = (int)x.size(3);
   auto y = at::empty({N, C}, x.options());
   avgpool_fwd(bp(x), bp(y), N, HW, C, cur());
@@ -395,6 +425,8 @@ at::Tensor avgpool_fwd_op(const at::Tensor& x) {
 
 at::Tensor avgpool_bwd_op(const at::Tensor& dy, at::IntArrayRef xshape) {
   check_bf16(dy, "dy", 2);
+  TORCH_CHECK(xshape.size() == 4 && xshape[0] == dy.size(0) && xshape[3] == dy.size(1) && xshape[1] * xshape[2] > 0 &&
+                  dy.numel() > 0, "avgpool_bwd: xshape [N,H,W,C] with dy [N,C], non-empty");
   auto dx = at::empty(xshape, dy.options());
   avgpool_bwd(bp(dy), bp(dx), (int)xshape[0], (int)(xshape[1] * xshape[2]), (int)xshape[3], cur());
   return dx;
