@@ -37,11 +37,29 @@ const float* clip_factor(const at::Tensor& t, const char* who) {
   return (const float*)t.data_ptr();
 }
 
+// The optional trailing ema / ema_decay / ema_num_updates of the flat optimizers: the moving average
+// of the weights, updated by the same launch from p' (csrc/ema.h). Checks the shadow and the decay.
+float* ema_shadow(const at::Tensor& e, const at::Tensor& p, double decay, const char* who) {
+  TORCH_CHECK(e.is_cuda() && e.scalar_type() == at::kFloat && e.is_contiguous() && e.numel() == p.numel(), who,
+              ": ema is a contiguous fp32 GPU tensor of p's size");
+  TORCH_CHECK(decay > 0.0 && decay < 1.0, who, ": ema_decay must be in (0, 1), got ", decay);
+  return (float*)e.data_ptr();
+}
+// the clip factor of the EMA variants when the caller clips nothing: one fp32 1.0 per device, made once
+const float* unit_scale(const at::Tensor& like) {
+  static at::Tensor one[64];
+  const int d = like.get_device();
+  TORCH_CHECK(d >= 0 && d < 64, "device index");
+  if (!one[d].defined()) one[d] = at::ones({1}, like.options().dtype(at::kFloat));
+  return (const float*)one[d].data_ptr();
+}
+
 // Adam's t = *step + t_offset; the schedule is evaluated on the device at s = t - 1
 void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf, double lr,
                double b1, double b2, double eps, at::Tensor step, double grad_scale, int64_t t_offset,
                std::string lr_kind, std::vector<double> lr_params, std::vector<int64_t> lr_boundaries,
-               std::vector<double> lr_values, c10::optional<at::Tensor> gscale) {
+               std::vector<double> lr_values, c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> ema,
+               double ema_decay, bool ema_num_updates) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "adam_flat: fp32 GPU params");
   TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel() && g.numel() == p.numel(), "adam_flat: sizes");
   TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam_flat: int64 GPU step");
@@ -50,8 +68,15 @@ void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::opti
              pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
              flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
              (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
-  if (gscale) adam_apply_clip(AdamClipArgs{a, clip_factor(*gscale, "adam_flat")}, cur());
-  else adam_apply(a, cur());
+  if (ema) {
+    const AdamClipArgs k{a, gscale ? clip_factor(*gscale, "adam_flat") : unit_scale(p)};
+    adam_apply_ema(AdamEmaArgs{k, ema_shadow(*ema, p, ema_decay, "adam_flat"), (float)ema_decay, ema_num_updates ? 1 : 0},
+                   cur());
+  } else if (gscale) {
+    adam_apply_clip(AdamClipArgs{a, clip_factor(*gscale, "adam_flat")}, cur());
+  } else {
+    adam_apply(a, cur());
+  }
 }
 
 void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
@@ -70,6 +95,41 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
             step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
   if (gscale) sgd_apply_clip(SgdClipArgs{a, clip_factor(*gscale, "momentum_flat")}, cur());
   else sgd_apply(a, cur());
+}
+
+// momentum_flat with the moving average of the weights updated by the same launch (csrc/ema.h): the
+// same arguments, then the shadow, its decay and whether the decay follows the step. An op of its own;
+// momentum_flat itself is what it was.
+void momentum_ema_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
+                       double lr, double momentum, double weight_decay, bool nesterov, double grad_scale,
+                       c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind,
+                       std::vector<double> lr_params, std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
+                       c10::optional<at::Tensor> gscale, at::Tensor ema, double ema_decay, bool ema_num_updates) {
+  const char* who = "momentum_ema_flat";
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
+  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), who, ": int64 GPU step");
+  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
+  TORCH_CHECK(sc.kind == LR_CONSTANT || step, who, ": a schedule needs the device step tensor");
+  TORCH_CHECK(!ema_num_updates || step, who, ": ema_num_updates needs the device step tensor");
+  TORCH_CHECK(g.numel() == p.numel() && (!mom || mom->numel() == p.numel()) && (!pbf || pbf->numel() == p.numel()), who,
+              ": sizes");
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  SgdArgs a{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
+            pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
+            sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
+            step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
+  const SgdClipArgs k{a, gscale ? clip_factor(*gscale, who) : unit_scale(p)};
+  sgd_apply_ema(SgdEmaArgs{k, ema_shadow(ema, p, ema_decay, who), (float)ema_decay, ema_num_updates ? 1 : 0}, cur());
+}
+
+// The shadow update as a pass of its own, from parameters already updated: e' = e - (1 - d_t)(e - p),
+// t = *step + t_offset (no step: t_offset). The same device helper as the fused variants.
+void ema_flat(at::Tensor e, at::Tensor p, double decay, bool num_updates, c10::optional<at::Tensor> step,
+              int64_t t_offset) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "ema_flat: fp32 GPU params");
+  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), "ema_flat: int64 GPU step");
+  ema_apply(ema_shadow(e, p, decay, "ema_flat"), (const float*)p.data_ptr(), p.numel(), (float)decay, num_updates ? 1 : 0,
+            step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset, cur());
 }
 
 // {norm, scale} of tf.clip_by_global_norm over a flat fp32 or bf16 buffer, on the device:
@@ -127,13 +187,21 @@ TORCH_LIBRARY(tfd, m) {
   m.impl("crc32c", c10::DispatchKey::CPU, &crc32c_op);
   m.def("adam_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, float lr, float b1, float b2, "
         "float eps, Tensor(e!) step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
-        "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], Tensor? gscale=None) -> ()");
+        "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], Tensor? gscale=None, "
+        "Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False) -> ()");
   m.impl("adam_flat", c10::DispatchKey::CUDA, &adam_flat);
   m.def("momentum_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
         "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
         "Tensor? gscale=None) -> ()");
   m.impl("momentum_flat", c10::DispatchKey::CUDA, &momentum_flat);
+  m.def("momentum_ema_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
+        "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
+        "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
+        "Tensor? gscale=None, *, Tensor(f!) ema, float ema_decay, bool ema_num_updates=False) -> ()");
+  m.impl("momentum_ema_flat", c10::DispatchKey::CUDA, &momentum_ema_flat);
+  m.def("ema_flat(Tensor(a!) e, Tensor p, float decay, bool num_updates=False, Tensor? step=None, int t_offset=0) -> ()");
+  m.impl("ema_flat", c10::DispatchKey::CUDA, &ema_flat);
   m.def("grad_global_norm(Tensor g, float clip_norm, float grad_scale=1.0) -> Tensor");
   m.impl("grad_global_norm", c10::DispatchKey::CUDA, &grad_global_norm);
   m.def("roofline_stream(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!) pbf, Tensor? x, int blocks, "

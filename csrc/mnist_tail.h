@@ -2,7 +2,9 @@
 // struct, with the device helpers it shares with csrc/kernels/mnist.hip. Two .hip files instantiate
 // it: mnist.hip with MnistAdamConst (optim_const.h: a constant rate -- the default path, the kernel
 // as it was before schedules) and mnist_tail_sched.hip with MnistAdamArgs (the LrSchedule evaluated
-// from the head kernel's t). They are separate code objects on purpose: the scheduled instantiation
+// from the head kernel's t). A third, mnist_tail_ema.hip, takes it over MnistAdamEmaArgs: the
+// scheduled instantiation plus the moving average of the weights, updated from p' while the tail holds
+// it in registers (ema.h). They are separate code objects on purpose: the scheduled instantiation
 // is twice the size, and inside mnist.hip's code object it would move every hot kernel of the default
 // step (docs/DESIGN.md section 9).
 #pragma once
@@ -59,8 +61,11 @@ constexpr int MAD_FC_BLOCKS = 1024;  // grid-stride blocks of the fc-region Adam
 constexpr int MAD_CONV = MAD_C1BLK + MAD_C2BLK;
 static_assert(MAD_C1F4 % 16 == 0, "conv1 region: whole blocks");
 constexpr int MAD_SL = 16;  // slab loads in flight per thread
-template <class Opt> __device__ __forceinline__ void adam4_pre(const Opt& o, int64_t i, f32x4 p, f32x4 m, f32x4 v,
-                                                               f32x4 g, float lr_t, float c1, float c2) {
+// em / e / omd (adam4: em / omd): the moving average of the weights (optim_const.h, ema.h), updated
+// from p' here -- empty tags unless the kernel's argument is the EMA wrapper
+template <class Opt, class E, class EV, class EO>
+__device__ __forceinline__ void adam4_pre(const Opt& o, int64_t i, f32x4 p, f32x4 m, f32x4 v, f32x4 g, float lr_t,
+                                          float c1, float c2, const E& em, EV e, EO omd) {
   m = m + (g - m) * c1;
   v = v + (g * g - v) * c2;
 #pragma unroll
@@ -69,11 +74,15 @@ template <class Opt> __device__ __forceinline__ void adam4_pre(const Opt& o, int
   reinterpret_cast<f32x4*>(o.m)[i] = m;
   reinterpret_cast<f32x4*>(o.v)[i] = v;
   if (o.pbf) reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
+  ema_store4(em, i, e, omd, p);
 }
-template <class Opt> __device__ __forceinline__ void adam4(const Opt& o, int64_t i, f32x4 g, float lr_t, float c1, float c2) {
+template <class Opt, class E, class EO>
+__device__ __forceinline__ void adam4(const Opt& o, int64_t i, f32x4 g, float lr_t, float c1, float c2, const E& em,
+                                      EO omd) {
   f32x4 p = reinterpret_cast<f32x4*>(o.p)[i];
   f32x4 m = reinterpret_cast<f32x4*>(o.m)[i];
   f32x4 v = reinterpret_cast<f32x4*>(o.v)[i];
+  const auto e = ema_load4(em, i);
   m = m + (g - m) * c1;
   v = v + (g * g - v) * c2;
 #pragma unroll
@@ -82,6 +91,7 @@ template <class Opt> __device__ __forceinline__ void adam4(const Opt& o, int64_t
   reinterpret_cast<f32x4*>(o.m)[i] = m;
   reinterpret_cast<f32x4*>(o.v)[i] = v;
   if (o.pbf) reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
+  ema_store4(em, i, e, omd, p);
 }
 // sum over slabs q, q + QS, ... (< ns) of float4 column x of a [ns][stride4] slab array; MAD_SL loads
 // issued per batch before any add
@@ -100,7 +110,14 @@ __device__ __forceinline__ f32x4 slab_sum(const f32x4* __restrict__ s4, int64_t 
   }
   return acc;
 }
-template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel(MnistStepArgs a, Opt o, int fcb4) {
+// the update's two scalars, both functions of t: Adam's rate and the shadow's 1 - d_t (an empty tag
+// without EMA)
+template <class EO> struct TailRates { float lr_t; EO omd; };
+// Opt: MnistAdamConst, MnistAdamArgs or MnistAdamEmaArgs (o: the struct itself or the one the wrapper
+// holds; em: the wrapper's shadow, else an empty tag)
+template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel(MnistStepArgs a, Opt oo, int fcb4) {
+  const auto& o = tail_args(oo);
+  const auto em = ema_of(oo);
   const int gb = gather_blocks(a);
   if ((int)blockIdx.x < gb) {  // the next step's batch; t = the step started next
     gather_next(a, *o.t, blockIdx.x);
@@ -114,7 +131,7 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
   auto lr_of = [&]() __attribute__((always_inline)) {  // (a call would wait for every load in flight)
     const int64_t t = *o.t;
     const float b1p = powf(o.beta1, (float)t), b2p = powf(o.beta2, (float)t);
-    return base_lr(o, t) * sqrtf(1.f - b2p) / (1.f - b1p);
+    return TailRates<decltype(ema_omd(em, t))>{base_lr(o, t) * sqrtf(1.f - b2p) / (1.f - b1p), ema_omd(em, t)};
   };
   const float c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
   const int bid = (int)blockIdx.x - gb, tid = threadIdx.x;
@@ -135,7 +152,8 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
       const int nq = one ? 16 : 4, qs = one ? 16 : 64;
       f32x4 s = red[x];
       for (int k = 1; k < nq; ++k) s += red[k * qs + x];
-      adam4(o, i, s, lr_of(), c1, c2);
+      const auto r = lr_of();
+      adam4(o, i, s, r.lr_t, c1, c2, em, r.omd);
     }
   } else {
     const int64_t i0 = fcb4 + (int64_t)(bid - MAD_CONV) * MAD_NT + tid;  // fcb4: MAD_C2END, or the out layer
@@ -145,10 +163,12 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
     // streaming non-temporal loads/stores were +0.9 us: the next step re-reads p/m/v from MALL)
     if (o.gbf) {
       constexpr int U = ADAM_U;
-      const float lr_t = lr_of();
+      const auto r = lr_of();
+      const float lr_t = r.lr_t;
       for (int64_t base = i0; base < TOTAL / 4; base += STRIDE * U) {
         uint2 h[U];
         f32x4 p[U], m[U], v[U];
+        decltype(ema_load4(em, 0)) e[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int64_t i = base + (int64_t)u * STRIDE;
@@ -157,6 +177,7 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
             h[u] = reinterpret_cast<const uint2*>(o.gbf)[i];
             m[u] = reinterpret_cast<const f32x4*>(o.m)[i];
             v[u] = reinterpret_cast<const f32x4*>(o.v)[i];
+            e[u] = ema_load4(em, i);
           }
         }
 #pragma unroll
@@ -173,22 +194,26 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
             reinterpret_cast<f32x4*>(o.m)[i] = m[u];
             reinterpret_cast<f32x4*>(o.v)[i] = v[u];
             reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[u][0], p[u][1]), pack_bf2(p[u][2], p[u][3]));
+            ema_store4(em, i, e[u], r.omd, p[u]);
           }
         }
       }
     } else {
       // the first item's p / m / v / g are loaded before t is awaited
       f32x4 p0 = {}, m0 = {}, v0 = {}, g0 = {};
+      decltype(ema_load4(em, 0)) e0{};
       if (i0 < TOTAL / 4) {
+        e0 = ema_load4(em, i0);
         p0 = reinterpret_cast<const f32x4*>(o.p)[i0];
         m0 = reinterpret_cast<const f32x4*>(o.m)[i0];
         v0 = reinterpret_cast<const f32x4*>(o.v)[i0];
         g0 = reinterpret_cast<const f32x4*>(a.grad)[i0];
       }
-      const float lr_t = lr_of();
-      if (i0 < TOTAL / 4) adam4_pre(o, i0, p0, m0, v0, g0, lr_t, c1, c2);
+      const auto r = lr_of();
+      const float lr_t = r.lr_t;
+      if (i0 < TOTAL / 4) adam4_pre(o, i0, p0, m0, v0, g0, lr_t, c1, c2, em, e0, r.omd);
       for (int64_t i = i0 + STRIDE; i < TOTAL / 4; i += STRIDE)
-        adam4(o, i, reinterpret_cast<const f32x4*>(a.grad)[i], lr_t, c1, c2);
+        adam4(o, i, reinterpret_cast<const f32x4*>(a.grad)[i], lr_t, c1, c2, em, r.omd);
     }
     if (bid == grid - 1 && tid == 0) *o.step += 1;  // see MnistAdamArgs
   }

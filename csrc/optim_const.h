@@ -9,6 +9,8 @@
 // profiles/lr_schedule_bench_ab.log). The scheduled instantiations are compiled in .hip files of their
 // own (optim_sched.hip, mnist_tail_sched.hip), so the default path's code objects hold what they held.
 #pragma once
+#include "common.h"
+#include "ema.h"
 #include "tfd_kernels.h"
 
 namespace tfd {
@@ -82,5 +84,41 @@ template <class A>
 __device__ __forceinline__ float grad_mul(const A& a, NoClip) { return a.grad_scale; }
 template <class A>
 __device__ __forceinline__ float grad_mul(const A& a, float clip) { return a.grad_scale * clip; }
+
+// The moving average of the weights (ema.h), for the EMA wrappers (AdamEmaArgs / SgdEmaArgs /
+// MnistAdamEmaArgs, tfd_kernels.h): ema_of(k) is the shadow and its decay, ema_omd its 1 - d_t at
+// Adam's t, ema_load4 / ema_store4 the shadow's float4 beside p's, ema_update1 the scalar form. For
+// every other struct ema_of is an empty tag and each of these is empty, so those instantiations hold
+// the code they held.
+struct NoEma {};
+struct EmaRef { float* e; float decay; int num_updates; };
+template <class K>
+__device__ __forceinline__ NoEma ema_of(const K&) { return NoEma{}; }
+__device__ __forceinline__ EmaRef ema_of(const AdamEmaArgs& k) { return EmaRef{k.ema, k.decay, k.num_updates}; }
+__device__ __forceinline__ EmaRef ema_of(const SgdEmaArgs& k) { return EmaRef{k.ema, k.decay, k.num_updates}; }
+__device__ __forceinline__ EmaRef ema_of(const MnistAdamEmaArgs& k) { return EmaRef{k.ema, k.decay, k.num_updates}; }
+__device__ __forceinline__ const AdamArgs& optim_args(const AdamEmaArgs& k) { return k.k.a; }
+__device__ __forceinline__ const SgdArgs& optim_args(const SgdEmaArgs& k) { return k.k.a; }
+__device__ __forceinline__ float clip_load(const AdamEmaArgs& k) { return *k.k.gscale; }
+__device__ __forceinline__ float clip_load(const SgdEmaArgs& k) { return *k.k.gscale; }
+// the fused MNIST tail's view of its argument: the struct itself, or the one the EMA wrapper holds
+template <class O>
+__device__ __forceinline__ const O& tail_args(const O& o) { return o; }
+__device__ __forceinline__ const MnistAdamArgs& tail_args(const MnistAdamEmaArgs& k) { return k.o; }
+
+__device__ __forceinline__ NoEma ema_omd(NoEma, int64_t) { return NoEma{}; }
+__device__ __forceinline__ float ema_omd(const EmaRef& r, int64_t t) { return ema_omd_at(r.decay, r.num_updates, t); }
+__device__ __forceinline__ NoEma ema_load4(NoEma, int64_t) { return NoEma{}; }
+__device__ __forceinline__ f32x4 ema_load4(const EmaRef& r, int64_t i) { return reinterpret_cast<const f32x4*>(r.e)[i]; }
+__device__ __forceinline__ void ema_store4(NoEma, int64_t, NoEma, NoEma, const f32x4&) {}
+__device__ __forceinline__ void ema_store4(const EmaRef& r, int64_t i, f32x4 e, float omd, const f32x4& p) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) e[j] = ema_step(e[j], p[j], omd);
+  reinterpret_cast<f32x4*>(r.e)[i] = e;
+}
+__device__ __forceinline__ void ema_update1(NoEma, int64_t, NoEma, float) {}
+__device__ __forceinline__ void ema_update1(const EmaRef& r, int64_t i, float omd, float p) {
+  r.e[i] = ema_step(r.e[i], p, omd);
+}
 
 }  // namespace tfd

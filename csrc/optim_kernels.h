@@ -4,7 +4,9 @@
 // and optim_sched.hip with AdamArgs / SgdArgs (the LrSchedule evaluated from the device step counter
 // where t is consumed). A third, optim_clip.hip, takes them over AdamClipArgs / SgdClipArgs: the same
 // kernels with the gradient multiplier grad_scale * *gscale, the clip factor of global-norm clipping
-// read from the device (grad_norm.hip). Separate code objects on purpose: see mnist_tail.h.
+// read from the device (grad_norm.hip). A fourth, optim_ema.hip, takes them over AdamEmaArgs /
+// SgdEmaArgs: the clip variant plus the moving average of the weights, updated from p' while it is in
+// registers (ema.h). Separate code objects on purpose: see mnist_tail.h.
 #pragma once
 #include <math.h>
 
@@ -47,8 +49,11 @@ __device__ __forceinline__ AdamItem adam_load4(const A& a, int64_t i) {
   }
   return x;
 }
-template <class A, class C>
-__device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, C clip, float lr_t, float c1, float c2) {
+// em / xe / omd: the moving average of the weights (optim_const.h), its float4 loaded beside x and
+// its 1 - d_t -- empty tags unless K is an EMA wrapper
+template <class A, class C, class E, class EV, class EO>
+__device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, C clip, float lr_t, float c1, float c2,
+                                            const E& em, EV xe, EO omd) {
   const f32x4 g = x.g * grad_mul(a, clip);
   f32x4 p = x.p, m = x.m, v = x.v;
   m = m + (g - m) * c1;
@@ -59,6 +64,7 @@ __device__ __forceinline__ void adam_apply4(const A& a, int64_t i, AdamItem x, C
   reinterpret_cast<f32x4*>(a.m)[i] = m;
   reinterpret_cast<f32x4*>(a.v)[i] = v;
   if (a.pbf) reinterpret_cast<uint2*>(a.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
+  ema_store4(em, i, xe, omd, p);
 }
 // The optimizer kernels are templates over their argument struct: the constant-rate view (AdamConst
 // / SgdConst, optim_const.h: the default path, as it was before schedules) or the struct with the
@@ -73,16 +79,25 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(K k) {
   const int64_t n4 = a.n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
   const int64_t i0 = (int64_t)blockIdx.x * kOptThreads + threadIdx.x;
+  const auto em = ema_of(k);
   AdamItem x{};
-  if (i0 < n4) x = adam_load4(a, i0);
+  decltype(ema_load4(em, 0)) xe{};
+  if (i0 < n4) {
+    x = adam_load4(a, i0);
+    xe = ema_load4(em, i0);
+  }
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
   const auto clip = clip_load(k);  // a load like t: issued here, awaited with it
+  const auto omd = ema_omd(em, t);
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
   const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
   for (int64_t i = i0; i < n4; i += stride) {
-    if (i != i0) x = adam_load4(a, i);
-    adam_apply4(a, i, x, clip, lr_t, c1, c2);
+    if (i != i0) {
+      x = adam_load4(a, i);
+      xe = ema_load4(em, i);
+    }
+    adam_apply4(a, i, x, clip, lr_t, c1, c2, em, xe, omd);
   }
   // scalar tail (n % 4)
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
@@ -92,6 +107,7 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(K k) {
     const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
     a.p[i] = p; a.m[i] = m; a.v[i] = v;
     if (a.pbf) a.pbf[i] = f2bf_bits(p);
+    ema_update1(em, i, omd, p);
   }
 }
 
@@ -115,17 +131,26 @@ __global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(K k, AdamRange
     return r.beg4[k] + (i - r.pre4[k]);
   };
   int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x;
+  const auto em = ema_of(k);
   AdamItem x{};
-  if (i < r.pre4[r.nr]) x = adam_load4(a, phys(i));
+  decltype(ema_load4(em, 0)) xe{};
+  if (i < r.pre4[r.nr]) {
+    x = adam_load4(a, phys(i));
+    xe = ema_load4(em, phys(i));
+  }
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
   const auto clip = clip_load(k);
+  const auto omd = ema_omd(em, t);
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
   const float c1 = 1.f - a.beta1, c2 = 1.f - a.beta2;
   for (; i < r.pre4[r.nr]; i += stride) {
     const int64_t pi = phys(i);
-    if (i != (int64_t)blockIdx.x * kOptThreads + threadIdx.x) x = adam_load4(a, pi);
-    adam_apply4(a, pi, x, clip, lr_t, c1, c2);
+    if (i != (int64_t)blockIdx.x * kOptThreads + threadIdx.x) {
+      x = adam_load4(a, pi);
+      xe = ema_load4(em, pi);
+    }
+    adam_apply4(a, pi, x, clip, lr_t, c1, c2, em, xe, omd);
   }
   if (blockIdx.x == 0 && threadIdx.x < r.tail_n) {
     const int64_t i = r.tail_beg + threadIdx.x;
@@ -135,17 +160,26 @@ __global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(K k, AdamRange
     const float p = a.p[i] - lr_t * m / (sqrtf(v) + a.eps);
     a.p[i] = p; a.m[i] = m; a.v[i] = v;
     if (a.pbf) a.pbf[i] = f2bf_bits(p);
+    ema_update1(em, i, omd, p);
   }
 }
 
+// the shadow's 1 - d_t of an SGD update: t = *step + t_offset, as the schedule reads it
+template <class A>
+__device__ __forceinline__ NoEma sgd_ema_omd(const A&, NoEma) { return NoEma{}; }
+__device__ __forceinline__ float sgd_ema_omd(const SgdArgs& a, const EmaRef& em) {
+  return ema_omd(em, (a.step ? *a.step : 0) + a.t_offset);
+}
 // GradientDescent / Momentum (TF ApplyMomentum: accum = accum*mu + g; p -= lr*accum,
 // nesterov: p -= lr*(g + mu*accum)); optional decoupled-from-nothing L2 weight decay folded in g.
-template <class K>  // SgdConst, SgdArgs or SgdClipArgs
+template <class K>  // SgdConst, SgdArgs, SgdClipArgs or SgdEmaArgs
 __global__ __launch_bounds__(kOptThreads) void sgd_kernel(K k) {
   const auto& a = optim_args(k);
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
   const float lr = base_lr(a);
   const auto clip = clip_load(k);
+  const auto em = ema_of(k);
+  const auto omd = sgd_ema_omd(a, em);
   for (int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {
     float g = (a.gbf ? bf2f(a.gbf[i]) : a.g[i]) * grad_mul(a, clip) + a.weight_decay * a.p[i];
     float p = a.p[i];
@@ -158,6 +192,7 @@ __global__ __launch_bounds__(kOptThreads) void sgd_kernel(K k) {
     }
     a.p[i] = p;
     if (a.pbf) a.pbf[i] = f2bf_bits(p);
+    ema_update1(em, i, omd, p);
   }
 }
 

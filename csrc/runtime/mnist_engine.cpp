@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 
+#include "../ema.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
@@ -186,6 +187,47 @@ class MnistEngine : public torch::CustomClassHolder {
   double clip_norm() const { return clip_norm_; }
   // {norm, scale} of the last clipped step, on the device ({0, 1} before the first)
   at::Tensor grad_norm() { return gnorm_; }
+  // tf.train.ExponentialMovingAverage of the weights (SyncReplicasOptimizer's variable_averages),
+  // updated by the optimizer kernels themselves from p' in registers (csrc/ema.h): e' = e - (1 - d_t)
+  // (e - p'), d_t = decay or, with num_updates, min(decay, (1 + t) / (10 + t)) from the device step
+  // counter, so a captured multi-step graph follows it. Every optimizer launch of every schedule takes
+  // its EMA variant; launches, streams and events are what they are without it. decay <= 0 turns it
+  // off (the default: nothing is allocated and the step is launch for launch what it was). Switching
+  // it on copies the parameters into the shadow (no zero-debias); after writing params() call
+  // load_ema(params()) to start the average again. Baked into graphs captured before the call.
+  void set_ema(double decay, bool num_updates) {
+    TORCH_CHECK(decay == decay && decay < 1.0, "set_ema: decay must be in (0, 1) (<= 0: off), got ", decay);
+    if (!(decay > 0)) {
+      ema_decay_ = 0.0;
+      return;
+    }
+    if (!ema_.defined()) {
+      ema_ = at::empty_like(params_);
+      one_ = at::ones({1}, params_.options());  // the clip factor of the EMA variants without clipping
+    }
+    if (!ema_on()) {
+      ema_.copy_(params_);
+      ema_bf_stale_ = true;
+    }
+    ema_decay_ = decay;
+    ema_nu_ = num_updates;
+  }
+  double ema_decay() const { return ema_decay_; }
+  // d_t of the update that ends at global_step = t (host evaluation of the device function)
+  double ema_decay_at_step(int64_t t) const { return (double)ema_decay_at((float)ema_decay_, ema_nu_ ? 1 : 0, t); }
+  // the fp32 flat shadow (shares storage with the engine). Like params() it is whole between steps:
+  // the deferred fc-region optimizer of the DP step, which writes both, is joined at every step's or
+  // graph's end.
+  at::Tensor ema_params() {
+    TORCH_CHECK(ema_.defined(), "ema_params: set_ema first");
+    return ema_;
+  }
+  void load_ema(at::Tensor t) {
+    TORCH_CHECK(ema_.defined(), "load_ema: set_ema first");
+    TORCH_CHECK(t.numel() == TOTAL, "load_ema: ", TOTAL, " elements");
+    ema_.copy_(t.reshape({TOTAL}));
+    ema_bf_stale_ = true;
+  }
   void set_comm(c10::intrusive_ptr<RcclComm> comm, bool bf16_grads) {
     comm_ = comm;
     bf16_comm_ = bf16_grads && !fp32_;
@@ -359,8 +401,18 @@ class MnistEngine : public torch::CustomClassHolder {
                              const int64_t* tsrc = nullptr) {
     if (!tsrc) tsrc = (const int64_t*)step_.data_ptr();
     const bool bf_grads = bf16_comm_ && dp();
+    if (ema_on()) {  // the same launch, with the shadow's update (optim_ema.hip)
+      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
+      else sgd_apply_ema(ema_args(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
+      return;
+    }
     if (opt_ == 0) adam_apply(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
     else sgd_apply(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
+  }
+  // Adam over up to 3 ranges of the flat buffers in one launch (o: buffer bases)
+  void apply_adam_ranges(const AdamArgs& o, int nr, const int64_t* beg, const int64_t* n, hipStream_t s) {
+    if (ema_on()) adam_ranges_ema(ema_args(o, 0), nr, beg, n, s);
+    else adam_apply_ranges(o, nr, beg, n, s);
   }
 
   // Full synchronous data-parallel step (the reference's SyncReplicasOptimizer global step with
@@ -377,6 +429,9 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(clip_norm_ > 0 && (zero_ || sfb_active())), "set_clip_norm conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the global norm needs the whole aggregated gradient on every rank; use the all-reduce schedule");
+    // each rank updates only its fc1 shard, so it would own only that shard of the averages
+    TORCH_CHECK(!(ema_on() && zero_), "set_ema conflicts with ZeRO-1 (set_zero): each rank would hold only its fc1 "
+                "shard of the moving averages; use a schedule without ZeRO");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -425,7 +480,8 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("conv_bwd", s);
     if (fused) {
       mark(P_BCONV, s);
-      mnist_adam_fused(a, o, s, true);
+      if (ema_on()) mnist_adam_fused_ema(a, ema_args(o), s, true);
+      else mnist_adam_fused(a, o, s, true);
       tag("opt", s);
     } else {
       mnist_conv_grad_reduce(a, s);
@@ -569,17 +625,17 @@ class MnistEngine : public torch::CustomClassHolder {
         const int64_t n[3] = {end[0] - beg[0], end[1] - beg[1], end[2] - beg[2]};
         const AdamArgs o = adam_args(0, 0, bf16_comm_, scale, 0, t);  // buffer bases; n comes per range
         if (split_opt) {
-          adam_apply_ranges(o, 2, beg + 1, n + 1, s);
+          apply_adam_ranges(o, 2, beg + 1, n + 1, s);
           tag("opt_fc", s);
           // the updated shard can leave now: the gather queues behind the conv bucket's all-reduce on
           // the comm stream and runs beside the conv-region Adam and the next conv forward
           gather_weights(s, "wag<-opt_fc");
           wag_issued_ = true;
           wait(s, ev_done_, "opt_conv<-ar_conv");
-          adam_apply_ranges(o, 1, beg, n, s);
+          apply_adam_ranges(o, 1, beg, n, s);
           tag("opt_conv", s);
         } else {
-          adam_apply_ranges(o, 3, beg, n, s);
+          apply_adam_ranges(o, 3, beg, n, s);
           tag("opt", s);
         }
       } else {
@@ -630,7 +686,8 @@ class MnistEngine : public torch::CustomClassHolder {
       // no bf16 shadow: nothing in fp32 mode reads it (set_dtype("bf16") re-derives it), and its
       // 6.5 MB of writes are 1 us of the bandwidth-bound optimizer tail
       mark(P_BCONV, s);
-      mnist_adam_fused(r, fused_adam_args(nullptr, false), s, true);
+      if (ema_on()) mnist_adam_fused_ema(r, ema_args(fused_adam_args(nullptr, false)), s, true);
+      else mnist_adam_fused(r, fused_adam_args(nullptr, false), s, true);
       mark(P_OPT, s);
       return;
     }
@@ -730,8 +787,14 @@ class MnistEngine : public torch::CustomClassHolder {
     grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
     grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
     tag("grad_norm", s);
-    if (opt_ == 0) adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
-    else sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+    if (ema_on()) {
+      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
+      else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
+    } else if (opt_ == 0) {
+      adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+    } else {
+      sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+    }
     tag("opt", s);
     mark(P_OPT, s);
   }
@@ -788,9 +851,18 @@ class MnistEngine : public torch::CustomClassHolder {
 
   // Evaluate on an explicit batch (x [n,784] fp32, y [n] int32) in chunks of <= B.
   // Returns a 2-element fp32 GPU tensor {sum of per-example loss, number correct}.
-  at::Tensor evaluate(at::Tensor x, at::Tensor y) {
+  // use_ema: the forward reads the moving averages (set_ema) in place of the parameters -- the fp32
+  // shadow or, in bf16, a bf16 image of it, cast here when a step or load_ema has made it stale (the
+  // step does not write it).
+  at::Tensor evaluate(at::Tensor x, at::Tensor y, bool use_ema) {
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.size(1) == 784, "x: [n,784] fp32 GPU");
     TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kInt, "y: [n] int32 GPU");
+    TORCH_CHECK(!use_ema || ema_on(), "evaluate(use_ema): set_ema first");
+    if (use_ema && !fp32_) {
+      if (!ema_bf_.defined()) ema_bf_ = at::empty_like(pbf_);
+      if (ema_bf_stale_) cast_f32_bf16((const float*)ema_.data_ptr(), (uint16_t*)ema_bf_.data_ptr(), TOTAL, stream());
+      ema_bf_stale_ = false;
+    }
     x = x.contiguous();
     y = y.contiguous();
     const int64_t n = x.size(0);
@@ -803,6 +875,7 @@ class MnistEngine : public torch::CustomClassHolder {
         f.data = (const float*)x.data_ptr() + o * 784;
         f.labels = (const int*)y.data_ptr() + o;
         f.perm = nullptr;
+        if (use_ema) f.p32 = (const float*)ema_.data_ptr();
         mnist_f32_forward(f, false, stream());
       } else {
         MnistStepArgs a = args();
@@ -810,6 +883,10 @@ class MnistEngine : public torch::CustomClassHolder {
         a.data = (const float*)x.data_ptr() + o * 784;
         a.labels = (const int*)y.data_ptr() + o;
         a.perm = nullptr;
+        if (use_ema) {
+          a.p32 = (const float*)ema_.data_ptr();
+          a.pbf = (const uint16_t*)ema_bf_.data_ptr();
+        }
         mnist_forward(a, false, stream());
       }
       out[0] += loss_row_.narrow(0, 0, nb).sum();
@@ -848,6 +925,7 @@ class MnistEngine : public torch::CustomClassHolder {
     auto it = graphs_.find(name);
     TORCH_CHECK(it != graphs_.end(), "no graph named ", name);
     hipStream_t s = stream();
+    ema_bf_stale_ = true;
     for (int64_t i = 0; i < times; ++i) HIP_OK(hipGraphLaunch(it->second, s));
   }
   void drop_graph(const std::string& name) {
@@ -1018,6 +1096,24 @@ class MnistEngine : public torch::CustomClassHolder {
     return MnistAdamArgs{(float*)params_.data_ptr(), (float*)m_.data_ptr(), (float*)v_.data_ptr(), pbf, sched_,
                          (float)b1_, (float)b2_, (float)eps_, (const int64_t*)tnext_.data_ptr(),
                          (int64_t*)step_.data_ptr(), bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr};
+  }
+  // The EMA variants' arguments (set_ema): the clip wrapper -- gscale the step's clip factor, or a
+  // device 1.0f without clipping -- and the shadow at the range's start. Each marks the bf16 image of
+  // the shadow stale: an EMA launch is about to move the shadow.
+  bool ema_on() const { return ema_decay_ > 0; }
+  AdamEmaArgs ema_args(const AdamArgs& a, int64_t beg, const float* gscale = nullptr) {
+    ema_bf_stale_ = true;
+    return AdamEmaArgs{AdamClipArgs{a, gscale ? gscale : (const float*)one_.data_ptr()}, (float*)ema_.data_ptr() + beg,
+                       (float)ema_decay_, ema_nu_ ? 1 : 0};
+  }
+  SgdEmaArgs ema_args(const SgdArgs& a, int64_t beg, const float* gscale = nullptr) {
+    ema_bf_stale_ = true;
+    return SgdEmaArgs{SgdClipArgs{a, gscale ? gscale : (const float*)one_.data_ptr()}, (float*)ema_.data_ptr() + beg,
+                      (float)ema_decay_, ema_nu_ ? 1 : 0};
+  }
+  MnistAdamEmaArgs ema_args(const MnistAdamArgs& o) {
+    ema_bf_stale_ = true;
+    return MnistAdamEmaArgs{o, (float*)ema_.data_ptr(), (float)ema_decay_, ema_nu_ ? 1 : 0};
   }
   // bf16 DP steps: the head kernel writes the optimizer's t, the slab reduce bumps the step, and with
   // a bf16 wire format (bf) both buckets' gradients come out of the kernels as bf16 in gbf_
@@ -1268,6 +1364,12 @@ class MnistEngine : public torch::CustomClassHolder {
   // global-norm clipping (set_clip_norm): 0 = off; {norm, scale} and stage 1's per-block partials
   double clip_norm_ = 0.0;
   at::Tensor gnorm_, gpart_;
+  // moving average of the weights (set_ema): 0 = off; the fp32 shadow, its bf16 image for
+  // evaluate(use_ema) (cast when stale) and the device 1.0f the EMA variants read as their clip factor
+  double ema_decay_ = 0.0;
+  bool ema_nu_ = false;
+  at::Tensor ema_, ema_bf_, one_;
+  bool ema_bf_stale_ = true;
   std::map<std::string, hipGraphExec_t> graphs_;
   // capture_topology: nodes added by each tagged operation (label@step -> node handles)
   bool topo_ = false;
@@ -1332,6 +1434,11 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("set_clip_norm", &MnistEngine::set_clip_norm)
       .def("clip_norm", &MnistEngine::clip_norm)
       .def("grad_norm", &MnistEngine::grad_norm)
+      .def("set_ema", &MnistEngine::set_ema)
+      .def("ema_decay", &MnistEngine::ema_decay)
+      .def("ema_decay_at_step", &MnistEngine::ema_decay_at_step)
+      .def("ema_params", &MnistEngine::ema_params)
+      .def("load_ema", &MnistEngine::load_ema)
       .def("set_comm", &MnistEngine::set_comm)
       .def("set_ipc", &MnistEngine::set_ipc)
       .def("set_ipc_gather", &MnistEngine::set_ipc_gather)
@@ -1361,7 +1468,7 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("apply_optimizer", &MnistEngine::apply_optimizer)
       .def("reduce_grads", &MnistEngine::reduce_grads)
       .def("train_step", &MnistEngine::train_step)
-      .def("evaluate", &MnistEngine::evaluate)
+      .def("evaluate", &MnistEngine::evaluate, "", {torch::arg("x"), torch::arg("y"), torch::arg("use_ema") = false})
       .def("capture_train_step", &MnistEngine::capture_train_step)
       .def("capture_train_steps", &MnistEngine::capture_train_steps)
       .def("capture_grads", &MnistEngine::capture_grads)

@@ -171,6 +171,24 @@ struct SgdClipArgs { SgdArgs a; const float* gscale; };
 void adam_apply_clip(const AdamClipArgs& a, hipStream_t s);
 void adam_ranges_clip(const AdamClipArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s);
 void sgd_apply_clip(const SgdClipArgs& a, hipStream_t s);
+// Exponential moving average of the weights, updated where the optimizer holds p' in registers
+// (ema.h: e' = fmaf(1 - d_t, p' - e, e), d_t from decay / num_updates and Adam's t). Wrappers over
+// the clip wrappers, so EMA composes with every schedule and with clipping through one variant: with
+// clipping off, gscale points at a device 1.0f (x * 1.0f is exact). `ema` is offset like p / m / v.
+// optim_ema.hip and mnist_tail_ema.hip hold the instantiations, code objects of their own.
+struct AdamEmaArgs { AdamClipArgs k; float* ema; float decay; int num_updates; };
+struct SgdEmaArgs { SgdClipArgs k; float* ema; float decay; int num_updates; };
+struct MnistAdamEmaArgs { MnistAdamArgs o; float* ema; float decay; int num_updates; };
+void adam_apply_ema(const AdamEmaArgs& a, hipStream_t s);
+void adam_ranges_ema(const AdamEmaArgs& a, int nr, const int64_t* beg, const int64_t* n, hipStream_t s);
+void sgd_apply_ema(const SgdEmaArgs& a, hipStream_t s);
+// the one-GPU tail with the shadow update; a null ema launches mnist_adam_fused itself
+void mnist_adam_fused_ema(const MnistStepArgs& a, const MnistAdamEmaArgs& o, hipStream_t s, bool fc_region = true);
+// Stand-alone shadow update over n elements from the parameters p already updated: the same helper,
+// t = *step + t_offset (step null: 0). For updates that are not one of these kernels, and the
+// reference the fused variants are held to bit for bit.
+void ema_apply(float* e, const float* p, int64_t n, float decay, int num_updates, const int64_t* step, int t_offset,
+               hipStream_t s);
 // Global gradient norm (grad_norm.hip), two plain launches, bit-identical run to run:
 //   grad_sumsq: sum of squares of n fp32 (g) or n bf16 (gbf, when non-null) elements as one fp32
 //     partial per block into partials[0, grad_norm_blocks(n)) -- a fixed grid, a function of n alone;

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --clip_norm --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --clip_norm --ema_decay --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -20,6 +20,7 @@ import torch  # noqa: E402
 
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
+from tensorflow_distributed_amd.training import checkpoint  # noqa: E402
 from tensorflow_distributed_amd.training.optimizers import AdamOptimizer  # noqa: E402
 from tensorflow_distributed_amd.utils import input_data  # noqa: E402
 
@@ -53,15 +54,30 @@ def main(argv=None):
                     "H2D) instead of the device-resident split with a per-epoch device shuffle")
     ap.add_argument("--clip_norm", type=float, default=0.0, help="tf.clip_by_global_norm on the gradient before "
                     "Adam (GPU: norm and clip factor taken on the device inside the step graph); 0 = off")
+    ap.add_argument("--ema_decay", type=float, default=0.0, help="tf.train.ExponentialMovingAverage of the weights, "
+                    "updated inside the optimizer after every step; 0 = off")
+    ap.add_argument("--ema_num_updates", type=int, default=1, help="--ema_decay: 1 = TF's num_updates=global_step, "
+                    "the decay of update t is min(ema_decay, (1 + t) / (10 + t))")
+    ap.add_argument("--ema_eval", type=int, default=1, help="--ema_decay: 1 = the final accuracy reads the averages")
+    ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
+                    "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
+    if a.ema_decay < 0 or a.ema_decay >= 1:
+        ap.error("--ema_decay must be in (0, 1) (0 = off)")
 
     # Import MNIST data (mnist_single.py:14-15)
     mnist = input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed)
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and not a.cpu) else torch.device("cpu")
-    opt = AdamOptimizer(a.learning_rate, clip_norm=a.clip_norm if a.clip_norm > 0 else None)
+    ema = dict(ema_decay=a.ema_decay, ema_num_updates=bool(a.ema_num_updates)) if a.ema_decay > 0 else {}
+    opt = AdamOptimizer(a.learning_rate, clip_norm=a.clip_norm if a.clip_norm > 0 else None, **ema)
     runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,
                          use_graph=not a.no_graph, dtype=a.dtype)
     runner.load_flat(M.flat_from_dict(M.init_params(a.seed)), {}, 0)  # init = initialize_all_variables()
+    saver = checkpoint.Saver()
+    latest = checkpoint.latest_checkpoint(a.logdir) if a.logdir else None
+    if latest:
+        runner.load_state_dict_tf(saver.restore(latest))
+        print("Restored %s (global step %d)" % (latest, runner.global_step()))
     device_input = dev.type == "cuda" and not a.host_feed
     if device_input:  # upload the split once; batches are gathered on the GPU (no per-step feed)
         runner.set_device_dataset(mnist.train.images, mnist.train.labels, seed=a.seed + 101)
@@ -89,14 +105,19 @@ def main(argv=None):
         print("Optimization Finished!")
         training_end_time = time.time()
         print("--- %s seconds Time for Training ---" % (training_end_time - start_time))
+        if a.logdir:
+            print("Saved %s" % saver.save(a.logdir, runner.state_dict_tf(), global_step=runner.global_step()))
     else:
         training_end_time = start_time
     # Calculate accuracy for 5000 mnist validation images
     nt = a.eval_batches
+    use_ema = a.ema_decay > 0 and bool(a.ema_eval)
+    if a.ema_decay > 0:
+        print("Accuracy from the %s" % ("moving averages (decay %g)" % a.ema_decay if use_ema else "variables"))
     accuracy_arr = []
     for counter in range(1, nt + 1):
         val_x, val_y = mnist.validation.next_batch(100)
-        _, correct = runner.evaluate(val_x, val_y)
+        _, correct = runner.evaluate(val_x, val_y, use_ema=use_ema)
         accuracy_arr.append(correct / float(len(val_x)))
     mean_accuracy = sum(accuracy_arr) / len(accuracy_arr)
     print("Mean Accuracy : %f" % mean_accuracy)

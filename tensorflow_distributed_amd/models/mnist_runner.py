@@ -19,8 +19,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..training.optimizers import FlatApplier, base_optimizer, is_schedule, lr_at, schedule_args
+from ..training.optimizers import FlatApplier, base_optimizer, ema_decay_at, is_schedule, lr_at, schedule_args
 from . import mnist_cnn as M
+
+
+EMA_SUFFIX = "/ExponentialMovingAverage"  # tf.train.ExponentialMovingAverage's shadow-variable name
 
 
 def _labels_to_ids(y) -> torch.Tensor:
@@ -45,6 +48,22 @@ class MnistRunnerBase:
         if step is None:
             step = self.global_step()
         return lr_at(self.opt.learning_rate, step)
+
+    # -- moving average of the weights (ema_decay on the optimizer config) --
+    @property
+    def ema_on(self) -> bool:
+        return bool(getattr(getattr(self, "opt", None), "ema_decay", None))
+
+    def current_ema_decay(self) -> float:
+        """``d_t`` of the LAST update, from the host's mirror of global_step (no device read)."""
+        step = getattr(self, "_hstep", None)
+        if step is None:
+            step = self.global_step()
+        return ema_decay_at(self.opt.ema_decay, step, self.opt.ema_num_updates)
+
+    def ema_params(self) -> torch.Tensor: ...
+    def load_ema(self, flat: torch.Tensor) -> None: ...
+    def reset_ema(self) -> None: ...
 
     # -- state (flat layout) --
     def params(self) -> torch.Tensor: ...
@@ -72,8 +91,12 @@ class MnistRunnerBase:
         out["global_step"] = np.array(step, dtype=np.int64)
         views = M.dict_from_flat(flat)
         slots = {k: M.dict_from_flat(v) for k, v in slot_t.items()}
+        # the Saver writes the shadow variables beside the variables they average
+        ema = M.dict_from_flat(self.ema_params().detach().float().cpu().clone()) if self.ema_on else None
         for key, tf_name, _ in M.PARAM_SPECS:
             out[tf_name] = views[key].numpy().copy()
+            if ema is not None:
+                out[tf_name + EMA_SUFFIX] = ema[key].numpy().copy()
             if "m" in slots:
                 out[tf_name + "/Adam"] = slots["m"][key].numpy().copy()
             if "v" in slots:
@@ -95,7 +118,14 @@ class MnistRunnerBase:
                     sflat = slots.setdefault(slot, torch.zeros(M.TOTAL))
                     M.dict_from_flat(sflat)[key].copy_(torch.from_numpy(np.asarray(tensors[tf_name + suffix])))
         step = int(np.asarray(tensors.get("global_step", 0)))
-        self.load_flat(flat, slots, step)
+        self.load_flat(flat, slots, step)  # (restarts the averages from the restored values)
+        # the averages, when the checkpoint carries all of them; with EMA off they are ignored
+        if self.ema_on and all(tf_name + EMA_SUFFIX in tensors for _, tf_name, _ in M.PARAM_SPECS):
+            eflat = torch.zeros(M.TOTAL)
+            eviews = M.dict_from_flat(eflat)
+            for key, tf_name, _ in M.PARAM_SPECS:
+                eviews[key].copy_(torch.from_numpy(np.asarray(tensors[tf_name + EMA_SUFFIX])))
+            self.load_ema(eflat)
 
     def slot_tensors(self) -> "dict":
         return {}
@@ -140,6 +170,19 @@ class TorchMnistRunner(MnistRunnerBase):
                 dst.copy_(t.to(self.device))
         self.applier.t = int(step)
         self._step = int(step)
+        self.reset_ema()
+
+    def ema_params(self) -> torch.Tensor:
+        assert self.ema_on, "ema_params: the optimizer config has no ema_decay"
+        if self.applier.ema is None:
+            self.applier.reset_ema(self.flat)
+        return self.applier.ema
+
+    def load_ema(self, flat) -> None:
+        self.applier.load_ema(flat.to(self.device))
+
+    def reset_ema(self) -> None:
+        self.applier.reset_ema(self.flat)
 
     def slot_tensors(self):
         s = self.applier.slots()
@@ -152,9 +195,10 @@ class TorchMnistRunner(MnistRunnerBase):
 
     def set_params(self, flat: torch.Tensor) -> None:
         self.flat.copy_(flat.to(self.device))
+        self.reset_ema()
 
-    def _forward(self, x, keep_prob, mask=None):
-        p = M.dict_from_flat(self.flat)
+    def _forward(self, x, keep_prob, mask=None, flat=None):
+        p = M.dict_from_flat(self.flat if flat is None else flat)
         return M.conv_net(x, p, keep_prob, dropout_mask=mask)
 
     def compute_grads(self, x, y) -> Tuple[torch.Tensor, float]:
@@ -204,10 +248,11 @@ class TorchMnistRunner(MnistRunnerBase):
         return {"allreduce_ms": round(ms, 4)} if ms is not None else {}
 
     @torch.no_grad()
-    def evaluate(self, x, y) -> Tuple[float, int]:
+    def evaluate(self, x, y, use_ema: bool = False) -> Tuple[float, int]:
+        """``use_ema``: the forward reads the moving averages in place of the parameters."""
         x = _as_f32(x).to(self.device)
         y = _labels_to_ids(y).to(self.device).long()
-        logits = self._forward(x, 1.0)
+        logits = self._forward(x, 1.0, flat=self.ema_params() if use_ema else None)
         loss = F.cross_entropy(logits, y, reduction="sum").item()
         return float(loss), int((logits.argmax(1) == y).sum().item())
 
@@ -245,6 +290,10 @@ class NativeMnistRunner(MnistRunnerBase):
         if comm is not None:
             self.eng.set_comm(comm, bf16_grads)
         self.stream = torch.cuda.Stream(self.device)
+        if self.ema_on:
+            # the optimizer kernels update the shadow themselves from p' in registers (csrc/ema.h)
+            with torch.cuda.stream(self.stream):
+                self.eng.set_ema(float(o.ema_decay), bool(o.ema_num_updates))
         self.use_graph = use_graph
         self._graph_ready = False
         self._grads_graph = False
@@ -353,8 +402,25 @@ class NativeMnistRunner(MnistRunnerBase):
             if "v" in slots:
                 self.eng.adam_v().copy_(slots["v"].to(self.device))
             self.eng.step_tensor().fill_(int(step))
+            if self.ema_on:
+                self.eng.load_ema(self.eng.params())
         self.stream.synchronize()
         self._hstep = int(step)
+
+    def ema_params(self) -> torch.Tensor:
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return self.eng.ema_params()
+
+    def load_ema(self, flat) -> None:
+        if self.ema_on:
+            with torch.cuda.stream(self.stream):
+                self.eng.load_ema(flat.to(self.device))
+            self.stream.synchronize()
+
+    def reset_ema(self) -> None:
+        if self.ema_on:
+            with torch.cuda.stream(self.stream):
+                self.eng.load_ema(self.eng.params())
 
     def slot_tensors(self):
         self.stream.synchronize()
@@ -375,6 +441,8 @@ class NativeMnistRunner(MnistRunnerBase):
         with torch.cuda.stream(self.stream):
             self.eng.params().copy_(flat.to(self.device, non_blocking=True))
             self.eng.sync_shadow()
+            if self.ema_on:
+                self.eng.load_ema(self.eng.params())
 
     def broadcast_from(self, root: int = 0) -> None:
         """Chief init -> every worker (reference M6: init_op on PS vars; here an RCCL broadcast)."""
@@ -385,6 +453,8 @@ class NativeMnistRunner(MnistRunnerBase):
             self.comm.broadcast(self.eng.adam_m(), root)
             self.comm.broadcast(self.eng.adam_v(), root)
             self.comm.broadcast(self.eng.step_tensor(), root)
+            if self.ema_on:
+                self.comm.broadcast(self.eng.ema_params(), root)
             self.eng.sync_shadow()
         self.stream.synchronize()
         self._hstep = int(self.eng.step_tensor().item())
@@ -473,11 +543,12 @@ class NativeMnistRunner(MnistRunnerBase):
             self.eng.apply_optimizer(scale)
         self.stream.synchronize()
 
-    def evaluate(self, x, y) -> Tuple[float, int]:
+    def evaluate(self, x, y, use_ema: bool = False) -> Tuple[float, int]:
+        """``use_ema``: the forward reads the moving averages in place of the parameters."""
         x = _as_f32(x).to(self.device)
         y = _labels_to_ids(y).to(self.device)
         with torch.cuda.stream(self.stream):
-            r = self.eng.evaluate(x, y)
+            r = self.eng.evaluate(x, y, bool(use_ema))
         self.stream.synchronize()
         r = r.cpu()
         return float(r[0]), int(round(float(r[1])))

@@ -100,6 +100,7 @@ def broadcast_state(runner, src_worker: int = 0, group=None, group_src_rank: Opt
         return
     src = group_src_rank if group_src_rank is not None else src_worker
     tensors = [runner.params()] + list(runner.slot_tensors().values())
+    ema = runner.ema_params() if getattr(runner, "ema_on", False) else None  # read before params() is overwritten
     for t in tensors:
         buf = t.detach().cpu().contiguous()
         dist.broadcast(buf, src, group=group)
@@ -111,3 +112,7 @@ def broadcast_state(runner, src_worker: int = 0, group=None, group_src_rank: Opt
     runner.set_global_step(int(step.item()))
     if hasattr(runner, "eng"):
         runner.set_params(runner.params())
+    if ema is not None:  # the chief's averages (restored, or its initial copy of the parameters)
+        buf = ema.detach().cpu().contiguous()
+        dist.broadcast(buf, src, group=group)
+        runner.load_ema(buf)

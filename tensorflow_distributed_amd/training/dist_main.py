@@ -77,6 +77,13 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("clip_norm", 0.0, "tf.clip_by_global_norm on the aggregated (averaged) gradient before the "
                    "optimizer; on GPUs the norm and the clip factor are taken on the device inside the step "
                    "graph. 0 = off. Synchronous all-reduce training of --model mnist_cnn only")
+    f.DEFINE_float("ema_decay", 0.0, "tf.train.ExponentialMovingAverage of the weights (SyncReplicasOptimizer's "
+                   "variable_averages), updated inside the optimizer kernels after every aggregated update; "
+                   "0 = off. The checkpoint carries <var>/ExponentialMovingAverage")
+    f.DEFINE_boolean("ema_num_updates", True, "--ema_decay: TF's num_updates=global_step, the decay of update t is "
+                     "min(ema_decay, (1 + t) / (10 + t))")
+    f.DEFINE_boolean("ema_eval", True, "--ema_decay: --eval_at_steps, the validation prints and the final accuracy "
+                     "read the averages instead of the variables")
     f.DEFINE_boolean("sync_replicas", True, "Use the sync_replicas (synchronized replicas) mode, "
                      "wherein the parameter updates from workers are aggregated before applied to "
                      "avoid stale gradients")
@@ -180,11 +187,12 @@ def _make_optimizer():
 
     lr = _make_learning_rate()
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
+    ema = dict(ema_decay=FLAGS.ema_decay, ema_num_updates=bool(FLAGS.ema_num_updates)) if FLAGS.ema_decay > 0 else {}
     if FLAGS.optimizer == "sgd":
-        return GradientDescentOptimizer(lr, clip_norm=clip)
+        return GradientDescentOptimizer(lr, clip_norm=clip, **ema)
     if FLAGS.optimizer == "momentum":
-        return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip)
-    return AdamOptimizer(lr, clip_norm=clip)
+        return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip, **ema)
+    return AdamOptimizer(lr, clip_norm=clip, **ema)
 
 
 def check_clip_norm_flags(num_workers: int) -> None:
@@ -206,6 +214,29 @@ def check_clip_norm_flags(num_workers: int) -> None:
     if FLAGS.model != "mnist_cnn":
         raise ValueError("--clip_norm with --model %s: the ResNet runner's bucketed optimizer does not clip yet "
                          "(follow-up)" % FLAGS.model)
+
+
+def check_ema_flags(num_workers: int) -> None:
+    """--ema_decay averages the variables of synchronous all-reduce training, where every worker holds
+    them whole. The combinations it does not cover are flag errors, raised before any process group is
+    built, not silently unaveraged runs."""
+    if FLAGS.ema_decay < 0 or FLAGS.ema_decay >= 1:
+        raise ValueError("--ema_decay=%g: must be in (0, 1) (0 = off)" % FLAGS.ema_decay)
+    if not FLAGS.ema_decay > 0:
+        return
+    if not FLAGS.sync_replicas:
+        raise ValueError("--ema_decay with --sync_replicas=False: the variables live on the asynchronous parameter "
+                         "server, which keeps no averages (follow-up)")
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("--ema_decay with backup workers (--replicas_to_aggregate=%d < %d workers): the variables "
+                         "live on the accumulator's side, which keeps no averages (follow-up)" % (r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--ema_decay with --model %s: the ResNet runner's bucketed optimizer does not take the "
+                         "shadow yet (follow-up; the flat ops do)" % FLAGS.model)
+    if "zero" in FLAGS.dp_schedule:
+        raise ValueError("--ema_decay with --dp_schedule=%s: under ZeRO-1 each worker would hold only its fc1 shard "
+                         "of the averages; use a schedule without ZeRO" % FLAGS.dp_schedule)
 
 
 def host_identity() -> str:
@@ -425,7 +456,10 @@ def dp_candidates(device_type: str, dtype: str):
     if device_type == "cuda":
         # --clip_norm: the global norm needs the whole aggregated gradient on every rank, which the
         # SFB / ZeRO schedules never form (MnistEngine.set_clip_norm)
-        return list(SCH.MNIST_SCHEDULES) if dtype == "bf16" and not FLAGS.clip_norm > 0 else ["allreduce"]
+        if dtype != "bf16" or FLAGS.clip_norm > 0:
+            return ["allreduce"]
+        # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
+        return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
     return list(SCH.CPU_SCHEDULES)
 
 
@@ -606,6 +640,7 @@ def main(argv=None) -> int:
         raise ValueError("Must specify an explicit `task_index`")
 
     check_clip_norm_flags(len(FLAGS.worker_hosts.split(",")))
+    check_ema_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -661,13 +696,15 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     from ..utils.metrics import MetricsLogger, StepTimer, performance_table
     from ..utils.tracing import Watchdog, trace_range
     from .grad_sync import make_grad_sync
-    from .optimizers import SyncReplicasOptimizer, lr_at
+    from .optimizers import ExponentialMovingAverage, SyncReplicasOptimizer, ema_decay_at, lr_at
 
     sync, num_workers, is_chief = roles.sync, cluster.num_workers, FLAGS.task_index == 0
     learning_rate = opt.learning_rate  # a float, or a schedule of global_step
     device = _task_device()
     if sync:  # tf.train.SyncReplicasOptimizer's check of 1 <= replicas_to_aggregate <= total_num_replicas
-        SyncReplicasOptimizer(opt, replicas_to_aggregate=roles.r2a, total_num_replicas=num_workers).resolve(num_workers)
+        va = ExponentialMovingAverage(opt.ema_decay, opt.ema_num_updates) if opt.ema_decay else None
+        SyncReplicasOptimizer(opt, replicas_to_aggregate=roles.r2a, total_num_replicas=num_workers,
+                              variable_averages=va).resolve(num_workers)
 
     dp_sched = dp_probe = dp_source = rccl = None
     if sync and num_workers > 1 and not roles.ps_mode:
@@ -709,9 +746,15 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     dp_comm = transport.comm if transport is not None else None  # RCCL; the IPC transport has nothing to abort
     watchdog = Watchdog(FLAGS.step_timeout_secs, on_timeout=(dp_comm.abort if dp_comm is not None else None))
 
+    ema_eval = bool(opt.ema_decay) and FLAGS.ema_eval  # evaluation reads the averages
+    if is_chief and opt.ema_decay:
+        print("Worker %d: moving averages of the variables, decay %g%s; evaluation reads the %s" % (
+            FLAGS.task_index, opt.ema_decay, " (num_updates = global_step)" if opt.ema_num_updates else "",
+            "averages" if ema_eval else "variables"))
+
     def eval_batch():
         val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
-        return len(val_x), runner.evaluate(val_x, val_y)[1]
+        return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
 
     time_begin = _training_begins()
     local_step = 0
@@ -739,6 +782,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
             if FLAGS.clip_norm > 0:
                 rec["grad_norm"], rec["clip_scale"] = runner.last_grad_norm()
+            if opt.ema_decay:  # d_t of this step's update (host mirror)
+                rec["ema_decay"] = ema_decay_at(opt.ema_decay, step, opt.ema_num_updates)
             if phase_timing:
                 ph = runner.phase_times()
                 rec.update(ph)

@@ -28,6 +28,14 @@ Global-norm gradient clipping (``tf.clip_by_global_norm`` between ``compute_grad
 ``apply_gradients``): ``clip_norm`` on every optimizer config. :func:`clip_by_global_norm` is the fp64
 definition; the GPU engine takes the norm and the factor on the device inside the step graph
 (``csrc/kernels/grad_norm.hip``, ``optim_clip.hip``).
+
+Moving average of the weights (``tf.train.ExponentialMovingAverage``, the ``variable_averages`` of
+``SyncReplicasOptimizer``): ``ema_decay`` / ``ema_num_updates`` on every optimizer config. After each
+update ``e' = e - (1 - d_t)(e - p')`` with ``d_t = decay`` or, with ``num_updates``,
+``min(decay, (1 + t)/(10 + t))``, ``t`` = ``global_step`` after the update; no zero-debias, the shadow
+starts as a copy of the parameters. :func:`ema_decay_at` / :func:`ema_update` are the fp64 definition;
+the GPU optimizer kernels update the shadow themselves from ``p'`` in registers (``csrc/ema.h``,
+``optim_ema.hip``, ``mnist_tail_ema.hip``).
 """
 from __future__ import annotations
 
@@ -178,6 +186,42 @@ def schedule_args(lr: LearningRate):
     return lr.kind, p, [], []
 
 
+def _check_ema(decay) -> None:
+    if decay is not None and not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"ema decay must be in (0, 1), got {decay!r}")
+
+
+def ema_decay_at(decay: float, t: int, num_updates: bool = False) -> float:
+    """``d_t`` of the update that ends at ``global_step == t`` (Adam's ``t``), fp64: ``decay``, or with
+    ``num_updates`` (TF's ``num_updates=global_step``) ``min(decay, (1 + t) / (10 + t))``."""
+    d = float(decay)
+    if not 0.0 < d < 1.0:
+        raise ValueError(f"ema decay must be in (0, 1), got {decay!r}")
+    if not num_updates:
+        return d
+    return min(d, (1.0 + int(t)) / (10.0 + int(t)))
+
+
+def ema_update(e: torch.Tensor, p: torch.Tensor, decay: float, t: int, num_updates: bool = False) -> torch.Tensor:
+    """The shadow after the update that produced ``p`` and ended at ``global_step == t``, in fp64:
+    ``e - (1 - d_t) * (e - p)``."""
+    e64 = e.detach().to(torch.float64)
+    return e64 - (1.0 - ema_decay_at(decay, t, num_updates)) * (e64 - p.detach().to(torch.float64))
+
+
+@dataclass(frozen=True)
+class ExponentialMovingAverage:
+    """``tf.train.ExponentialMovingAverage(decay, num_updates=global_step)`` as a value: what
+    ``SyncReplicasOptimizer(variable_averages=...)`` takes. ``num_updates``: whether the decay follows
+    ``global_step`` (``min(decay, (1 + t)/(10 + t))``)."""
+    decay: float
+    num_updates: bool = False
+
+    def __post_init__(self):
+        if not 0.0 < float(self.decay) < 1.0:
+            raise ValueError(f"ema decay must be in (0, 1), got {self.decay!r}")
+
+
 @dataclass
 class AdamOptimizer:
     learning_rate: LearningRate = 0.001
@@ -187,6 +231,11 @@ class AdamOptimizer:
     name: str = "Adam"
     kind: str = field(default="adam", init=False)
     clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
 
 
 @dataclass
@@ -195,6 +244,11 @@ class GradientDescentOptimizer:
     name: str = "GradientDescent"
     kind: str = field(default="sgd", init=False)
     clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
 
 
 @dataclass
@@ -205,6 +259,11 @@ class MomentumOptimizer:
     name: str = "Momentum"
     kind: str = field(default="momentum", init=False)
     clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
 
 
 @dataclass
@@ -214,13 +273,23 @@ class SyncReplicasOptimizer:
     replicas_to_aggregate: Optional[int] = None
     total_num_replicas: Optional[int] = None
     name: str = "sync_replicas"
+    # TF's variable_averages (variables_to_average: every trainable variable): forwarded to the base
+    # optimizer's ema_decay / ema_num_updates, so the shadow is updated after every aggregated update
+    variable_averages: Optional[ExponentialMovingAverage] = None
+
+    def __post_init__(self):
+        va = self.variable_averages
+        if va is not None:
+            import dataclasses
+
+            self.opt = dataclasses.replace(self.opt, ema_decay=float(va.decay), ema_num_updates=bool(va.num_updates))
 
     def resolve(self, num_workers: int) -> "SyncReplicasOptimizer":
         r = self.replicas_to_aggregate if self.replicas_to_aggregate is not None else num_workers
         t = self.total_num_replicas if self.total_num_replicas is not None else num_workers
         if not 1 <= r <= t:
             raise ValueError(f"replicas_to_aggregate={r} must be in [1, total_num_replicas={t}]")
-        return SyncReplicasOptimizer(self.opt, r, t, self.name)
+        return SyncReplicasOptimizer(self.opt, r, t, self.name, self.variable_averages)
 
     @property
     def has_backup_workers(self) -> bool:
@@ -268,6 +337,9 @@ class FlatApplier:
         self.v = z() if k == "adam" else None
         self.last_grad_norm: Optional[float] = None  # norm / clip part of the last clipped apply()
         self.last_clip_scale: Optional[float] = None
+        # moving average of the weights (ema_decay on the config): starts as a copy of the parameters at
+        # the first apply(), or where reset_ema() / load_ema() put it
+        self.ema: Optional[torch.Tensor] = None
 
     @torch.no_grad()
     def apply(self, p: torch.Tensor, g: torch.Tensor, scale: float = 1.0) -> None:
@@ -277,6 +349,8 @@ class FlatApplier:
             self.last_clip_scale = factor / scale
             scale = factor
         g = g if scale == 1.0 else g * scale
+        if getattr(o, "ema_decay", None) and self.ema is None:
+            self.reset_ema(p)
         lr = lr_at(o.learning_rate, self.t)  # global_step before this update
         self.t += 1
         if o.kind == "adam":
@@ -293,6 +367,19 @@ class FlatApplier:
                 p.sub_(lr * self.m)
         else:
             p.sub_(lr * g)
+        if getattr(o, "ema_decay", None):
+            # the update itself ran with EMA off or on alike; the shadow follows p' in fp32
+            omd = 1.0 - ema_decay_at(o.ema_decay, self.t, o.ema_num_updates)
+            self.ema.add_(p - self.ema, alpha=omd)
+
+    def reset_ema(self, p: torch.Tensor) -> None:
+        """(Re)start the average as a copy of ``p`` (no zero-debias)."""
+        if getattr(self.opt, "ema_decay", None):
+            self.ema = p.detach().clone()
+
+    def load_ema(self, e: torch.Tensor) -> None:
+        if getattr(self.opt, "ema_decay", None):
+            self.ema = e.detach().to(torch.float32).clone()
 
     def slots(self) -> "OrderedDict[str, torch.Tensor]":
         out = OrderedDict()
