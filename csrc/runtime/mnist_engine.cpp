@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../ema.h"
+#include "../layerwise_kernels.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
@@ -155,11 +156,40 @@ class MnistEngine : public torch::CustomClassHolder {
 
   void set_adam(double lr, double b1, double b2, double eps) {
     opt_ = 0; b1_ = b1; b2_ = b2; eps_ = eps;
+    lw_ = 0;
     sched_ = lr_constant((float)lr);
   }
   void set_momentum(double lr, double momentum, bool nesterov) {
     opt_ = momentum > 0 ? 2 : 1; momentum_ = momentum; nesterov_ = nesterov;
+    lw_ = 0;
     sched_ = lr_constant((float)lr);
+  }
+  // Layer-wise optimizers (csrc/layerwise.h): every variable's update is scaled by a trust ratio formed
+  // from two L2 norms over that variable, taken on the device inside the step (three launches over
+  // one block table, kernels/optim_layerwise.hip). LAMB uses the Adam slots (adam_m / adam_v), LARS the
+  // momentum slot (adam_m), t = global_step after the update. skip_bias: the four biases take neither
+  // the weight decay nor the ratio (LARS's skip_list, LAMB's exclude_from_*). The step is the serial
+  // schedule of the clip step; set_clip_norm, set_ema and set_lr_schedule compose with it. set_adam /
+  // set_momentum switch back. Baked into graphs captured before the call: capture again.
+  void set_lamb(double lr, double b1, double b2, double eps, double weight_decay, bool skip_bias) {
+    TORCH_CHECK(weight_decay >= 0, "set_lamb: weight_decay >= 0");
+    opt_ = 0; b1_ = b1; b2_ = b2; eps_ = eps;
+    lw_wd_ = weight_decay;
+    sched_ = lr_constant((float)lr);
+    set_layerwise(1, skip_bias);
+  }
+  void set_lars(double lr, double momentum, double weight_decay, double eeta, double eps, bool skip_bias) {
+    TORCH_CHECK(weight_decay >= 0 && eeta > 0 && eps >= 0, "set_lars: weight_decay >= 0, eeta > 0, eps >= 0");
+    opt_ = 2; momentum_ = momentum; nesterov_ = false;
+    lw_wd_ = weight_decay; lw_eeta_ = eeta; lw_eps_ = eps;
+    sched_ = lr_constant((float)lr);
+    set_layerwise(2, skip_bias);
+  }
+  // [8,3] = {|p|, |u| (LAMB) or |g| (LARS), r} of the last layer-wise step, on the device, in the flat
+  // layout's order: wc1, bc1, wc2, bc2, wd1, bd1, out, out_b
+  at::Tensor layer_norms() {
+    TORCH_CHECK(lw_out_.defined(), "layer_norms: set_lamb or set_lars first");
+    return lw_out_;
   }
   // Learning rate as a function of global_step (csrc/lr_schedule.h), evaluated by the optimizer
   // kernels from the device step counter: a captured multi-step graph follows it with no host round
@@ -401,6 +431,12 @@ class MnistEngine : public torch::CustomClassHolder {
                              const int64_t* tsrc = nullptr) {
     if (!tsrc) tsrc = (const int64_t*)step_.data_ptr();
     const bool bf_grads = bf16_comm_ && dp();
+    if (lw_) {
+      TORCH_CHECK(beg == 0 && end == TOTAL, "a layer-wise optimizer updates the whole flat buffer: a range has no "
+                  "per-variable norm");
+      apply_layerwise(bf_grads, grad_scale, t_offset, tsrc, nullptr, s);
+      return;
+    }
     if (ema_on()) {  // the same launch, with the shadow's update (optim_ema.hip)
       if (opt_ == 0) adam_apply_ema(ema_args(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
       else sgd_apply_ema(ema_args(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
@@ -429,6 +465,10 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(clip_norm_ > 0 && (zero_ || sfb_active())), "set_clip_norm conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the global norm needs the whole aggregated gradient on every rank; use the all-reduce schedule");
+    // a sharded gradient has no per-variable norm either
+    TORCH_CHECK(!(lw_ && (zero_ || sfb_active())), lw_ == 1 ? "set_lamb" : "set_lars", " conflicts with ",
+                zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
+                ": the per-variable norms need the whole aggregated gradient on every rank; use the all-reduce schedule");
     // each rank updates only its fc1 shard, so it would own only that shard of the averages
     TORCH_CHECK(!(ema_on() && zero_), "set_ema conflicts with ZeRO-1 (set_zero): each rank would hold only its fc1 "
                 "shard of the moving averages; use a schedule without ZeRO");
@@ -440,7 +480,7 @@ class MnistEngine : public torch::CustomClassHolder {
     const bool dp = this->dp();
     timed_ = timing_;
     timed_dp_ = timing_ && dp;
-    if (clip_norm_ > 0) {
+    if (clip_norm_ > 0 || lw_) {
       train_step_clip(dp);
       return;
     }
@@ -707,10 +747,11 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_OPT, s);
   }
 
-  // Step with global-norm clipping (set_clip_norm): one serial schedule for both dtypes, the shape of
-  // the unfused one-GPU step --
+  // Step with global-norm clipping (set_clip_norm) and / or a layer-wise optimizer (set_lamb, set_lars):
+  // one serial schedule for both dtypes, the shape of the unfused one-GPU step --
   //   s: forward -> backward a -> backward b -> conv-slab reduce (step bump) -> [DP: wait c]
-  //      -> norm stage 1 -> norm stage 2 -> ONE optimizer over [0, TOTAL), t = global_step
+  //      -> [clip: norm stage 1 -> norm stage 2] -> ONE optimizer over [0, TOTAL), t = global_step
+  //         (layer-wise: its three stages, which need the whole aggregated gradient as the clip does)
   //   c (DP): [wait fc bwd] all-reduce A -> [wait slab reduce] all-reduce B  (fp32 dtype: one bucket)
   // The norm is taken of the aggregated gradient, in the buffer the optimizer reads (gbf_ with a bf16
   // wire), so N ranks at batch B stay equal to one at N*B. The fused one-GPU tail cannot host the clip:
@@ -784,10 +825,14 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     float* pair = (float*)gnorm_.data_ptr();
     float* part = (float*)gpart_.data_ptr();
-    grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
-    grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
-    tag("grad_norm", s);
-    if (ema_on()) {
+    if (clip_norm_ > 0) {
+      grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
+      grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
+      tag("grad_norm", s);
+    }
+    if (lw_) {
+      apply_layerwise(bf, scale, 0, step, clip_norm_ > 0 ? pair + 1 : nullptr, s);
+    } else if (ema_on()) {
       if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
       else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
     } else if (opt_ == 0) {
@@ -1097,6 +1142,75 @@ class MnistEngine : public torch::CustomClassHolder {
                          (float)b1_, (float)b2_, (float)eps_, (const int64_t*)tnext_.data_ptr(),
                          (int64_t*)step_.data_ptr(), bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr};
   }
+  // ---- layer-wise optimizers ----
+  // the variable table of the flat layout and its block table, built once, on the device
+  void set_layerwise(int kind, bool skip_bias) {
+    const int w = LW_DECAY | LW_ADAPT, b = skip_bias ? 0 : w;
+    const LwSegment segs[8] = {{OFF_WC1, KTAPS * C1, w}, {OFF_BC1, C1, b}, {OFF_WC2, KTAPS * C1 * C2, w}, {OFF_BC2, C2, b},
+                               {OFF_WD1, (int64_t)FEAT * HID, w}, {OFF_BD1, HID, b}, {OFF_OUT, HID * NCLS, w},
+                               {OFF_BOUT, NCLS, b}};
+    LwTable t;
+    try {
+      t = lw_build_table(segs, 8, kLwChunk, TOTAL);
+    } catch (const std::invalid_argument& e) {
+      TORCH_CHECK(false, e.what());
+    }
+    auto to_dev = [&](const void* src, size_t bytes) {
+      return at::from_blob(const_cast<void*>(src), {(int64_t)bytes}, at::TensorOptions().dtype(at::kByte))
+          .to(params_.device());
+    };
+    // written in place once they exist (the sizes depend on the layout alone): a graph captured
+    // earlier keeps pointing at live tables
+    if (lw_out_.defined()) {
+      lw_blocks_.copy_(to_dev(t.blocks.data(), t.blocks.size() * sizeof(LwBlock)));
+      lw_segs_.copy_(to_dev(t.segs.data(), t.segs.size() * sizeof(LwSegBlocks)));
+    } else {
+      lw_blocks_ = to_dev(t.blocks.data(), t.blocks.size() * sizeof(LwBlock));
+      lw_segs_ = to_dev(t.segs.data(), t.segs.size() * sizeof(LwSegBlocks));
+      lw_nblocks_ = (int)t.blocks.size();
+      // host tensors copied over: ready when the call returns, whichever stream the first step runs on
+      lw_part_ = at::empty({lw_nblocks_, 2}, params_.options());  // every entry is stored by every stage 1
+      lw_out_ = at::zeros({8, 3}, at::kFloat).to(params_.device());
+    }
+    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());  // the clip factor without clipping
+    lw_ = kind;
+  }
+  // stages 1, 2, 3 over [0, TOTAL); gscale: the step's clip factor on the device, null without clipping
+  void apply_layerwise(bool bf_grads, double grad_scale, int t_offset, const int64_t* t, const float* gscale,
+                       hipStream_t s) {
+    LayerwiseArgs a{};
+    a.p = (float*)params_.data_ptr();
+    a.s1 = (float*)m_.data_ptr();
+    a.s2 = lw_ == 1 ? (float*)v_.data_ptr() : nullptr;
+    a.g = bf_grads ? nullptr : (const float*)grad_.data_ptr();
+    a.gbf = bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr;
+    a.pbf = (uint16_t*)pbf_.data_ptr();
+    a.blocks = (const LwBlock*)lw_blocks_.data_ptr();
+    a.segs = (const LwSegBlocks*)lw_segs_.data_ptr();
+    a.nblocks = lw_nblocks_;
+    a.nsegs = 8;
+    a.partials = (float*)lw_part_.data_ptr();
+    a.out = (float*)lw_out_.data_ptr();
+    a.sched = sched_;
+    a.beta1 = (float)b1_;
+    a.beta2 = (float)b2_;
+    a.momentum = (float)momentum_;
+    a.eeta = (float)lw_eeta_;
+    a.eps = (float)(lw_ == 1 ? eps_ : lw_eps_);
+    a.weight_decay = (float)lw_wd_;
+    a.step = t;
+    a.t_offset = t_offset;
+    a.grad_scale = (float)grad_scale;
+    a.gscale = gscale ? gscale : (const float*)one_.data_ptr();
+    if (ema_on()) {
+      ema_bf_stale_ = true;
+      a.ema = (float*)ema_.data_ptr();
+      a.ema_decay = (float)ema_decay_;
+      a.ema_num_updates = ema_nu_ ? 1 : 0;
+    }
+    if (lw_ == 1) lamb_apply(a, s);
+    else lars_apply(a, s);
+  }
   // The EMA variants' arguments (set_ema): the clip wrapper -- gscale the step's clip factor, or a
   // device 1.0f without clipping -- and the shadow at the range's start. Each marks the bf16 image of
   // the shadow stale: an EMA launch is about to move the shadow.
@@ -1328,6 +1442,10 @@ class MnistEngine : public torch::CustomClassHolder {
   int fc1_splits_, wg2_splits_;
   int64_t input_mode_ = 0;
   int opt_ = 0;
+  // layer-wise optimizer (set_lamb / set_lars): 0 = off, 1 = LAMB, 2 = LARS; its tables and outputs
+  int lw_ = 0, lw_nblocks_ = 0;
+  double lw_wd_ = 0.0, lw_eeta_ = 0.0, lw_eps_ = 0.0;
+  at::Tensor lw_blocks_, lw_segs_, lw_part_, lw_out_;
   double b1_ = 0.9, b2_ = 0.999, eps_ = 1e-8, momentum_ = 0.0;
   LrSchedule sched_ = lr_constant(0.01f);
   bool nesterov_ = false;
@@ -1429,6 +1547,9 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)
       .def("set_momentum", &MnistEngine::set_momentum)
+      .def("set_lamb", &MnistEngine::set_lamb)
+      .def("set_lars", &MnistEngine::set_lars)
+      .def("layer_norms", &MnistEngine::layer_norms)
       .def("set_lr_schedule", &MnistEngine::set_lr_schedule)
       .def("lr_at_step", &MnistEngine::lr_at_step)
       .def("set_clip_norm", &MnistEngine::set_clip_norm)

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --clip_norm --ema_decay --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --ema_decay --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -21,7 +21,7 @@ import torch  # noqa: E402
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
 from tensorflow_distributed_amd.training import checkpoint  # noqa: E402
-from tensorflow_distributed_amd.training.optimizers import AdamOptimizer  # noqa: E402
+from tensorflow_distributed_amd.training.optimizers import AdamOptimizer, LAMBOptimizer, LARSOptimizer  # noqa: E402
 from tensorflow_distributed_amd.utils import input_data  # noqa: E402
 
 # Parameters (mnist_single.py:17-21)
@@ -54,6 +54,13 @@ def main(argv=None):
                     "H2D) instead of the device-resident split with a per-epoch device shuffle")
     ap.add_argument("--clip_norm", type=float, default=0.0, help="tf.clip_by_global_norm on the gradient before "
                     "Adam (GPU: norm and clip factor taken on the device inside the step graph); 0 = off")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb", "lars"], help="adam (the reference), or a "
+                    "layer-wise optimizer: every variable's update scaled by a trust ratio of two per-variable norms")
+    ap.add_argument("--weight_decay", type=float, default=-1.0, help="--optimizer lamb / lars: weight decay "
+                    "(default: 0 for lamb, 1e-4 for lars)")
+    ap.add_argument("--lars_eeta", type=float, default=1e-3, help="--optimizer lars: the trust coefficient")
+    ap.add_argument("--layerwise_skip_bias", type=int, default=1, help="--optimizer lamb / lars: 1 = the biases take "
+                    "neither the weight decay nor the trust ratio")
     ap.add_argument("--ema_decay", type=float, default=0.0, help="tf.train.ExponentialMovingAverage of the weights, "
                     "updated inside the optimizer after every step; 0 = off")
     ap.add_argument("--ema_num_updates", type=int, default=1, help="--ema_decay: 1 = TF's num_updates=global_step, "
@@ -69,7 +76,17 @@ def main(argv=None):
     mnist = input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed)
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and not a.cpu) else torch.device("cpu")
     ema = dict(ema_decay=a.ema_decay, ema_num_updates=bool(a.ema_num_updates)) if a.ema_decay > 0 else {}
-    opt = AdamOptimizer(a.learning_rate, clip_norm=a.clip_norm if a.clip_norm > 0 else None, **ema)
+    if a.optimizer == "adam" and a.weight_decay >= 0:
+        ap.error("--weight_decay belongs to --optimizer lamb / lars")
+    common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, **ema)
+    if a.optimizer != "adam":
+        common.update(skip_bias=bool(a.layerwise_skip_bias), **({} if a.weight_decay < 0 else dict(weight_decay=a.weight_decay)))
+    if a.optimizer == "lamb":
+        opt = LAMBOptimizer(a.learning_rate, **common)
+    elif a.optimizer == "lars":
+        opt = LARSOptimizer(a.learning_rate, eeta=a.lars_eeta, **common)
+    else:
+        opt = AdamOptimizer(a.learning_rate, **common)
     runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,
                          use_graph=not a.no_graph, dtype=a.dtype)
     runner.load_flat(M.flat_from_dict(M.init_params(a.seed)), {}, 0)  # init = initialize_all_variables()

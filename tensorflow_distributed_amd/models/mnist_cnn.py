@@ -60,6 +60,18 @@ def _numel(shape):
     return n
 
 
+def segments(skip_bias: bool = True):
+    """The variable table of the flat layout for the layer-wise optimizers (``csrc/layerwise.h``):
+    ``[(begin, length, flags)]`` in flat order (``wc1, bc1, wc2, bc2, wd1, bd1, out, out_b``). The four
+    weights take the weight decay and the trust ratio; with ``skip_bias`` the four biases take neither
+    (LARS's ``skip_list``, LAMB's ``exclude_from_weight_decay`` / ``exclude_from_layer_adaptation``).
+    The padding ``[NUM_PARAMS, TOTAL)`` belongs to no variable."""
+    from ..training.optimizers import LW_ADAPT, LW_DECAY
+
+    both = LW_DECAY | LW_ADAPT
+    return [(off, _numel(SHAPES[k]), both if (len(SHAPES[k]) > 1 or not skip_bias) else 0) for k, off in OFFSETS.items()]
+
+
 def init_params(seed: int = 0, dtype=torch.float32) -> Dict[str, torch.Tensor]:
     """N(0,1) init of every parameter in reference creation order (deterministic for a seed)."""
     g = torch.Generator().manual_seed(seed)

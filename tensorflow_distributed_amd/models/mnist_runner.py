@@ -19,11 +19,24 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..training.optimizers import FlatApplier, base_optimizer, ema_decay_at, is_schedule, lr_at, schedule_args
+from ..training.optimizers import (FlatApplier, base_optimizer, ema_decay_at, is_layerwise, is_schedule, lr_at,
+                                   schedule_args)
 from . import mnist_cnn as M
 
 
 EMA_SUFFIX = "/ExponentialMovingAverage"  # tf.train.ExponentialMovingAverage's shadow-variable name
+LAYER_NAMES = tuple(M.OFFSETS)  # the variables in flat-layout order: the rows of last_layer_norms()
+
+
+def _slot_suffixes(opt):
+    """``[(checkpoint suffix, slot)]`` by TF's slot-variable rule: a slot is saved as
+    ``<var>/<optimizer name>``, a second one as ``<var>/<optimizer name>_1``."""
+    kind = getattr(opt, "kind", "adam")
+    if kind == "lamb":
+        return [("/" + opt.name, "m"), ("/" + opt.name + "_1", "v")]
+    if kind == "lars":
+        return [("/" + opt.name, "accum")]
+    return [("/Adam", "m"), ("/Adam_1", "v"), ("/Momentum", "accum")]
 
 
 def _labels_to_ids(y) -> torch.Tensor:
@@ -61,6 +74,16 @@ class MnistRunnerBase:
             step = self.global_step()
         return ema_decay_at(self.opt.ema_decay, step, self.opt.ema_num_updates)
 
+    # -- layer-wise optimizers (LAMB, LARS) --
+    @property
+    def layerwise(self) -> bool:
+        return is_layerwise(getattr(self, "opt", None))
+
+    def last_layer_norms(self) -> "dict":
+        """``{variable: (|p|, |u| or |g|, trust ratio)}`` of the last update, in flat-layout order; empty
+        without a layer-wise optimizer or before the first update."""
+        return {}
+
     def ema_params(self) -> torch.Tensor: ...
     def load_ema(self, flat: torch.Tensor) -> None: ...
     def reset_ema(self) -> None: ...
@@ -97,12 +120,9 @@ class MnistRunnerBase:
             out[tf_name] = views[key].numpy().copy()
             if ema is not None:
                 out[tf_name + EMA_SUFFIX] = ema[key].numpy().copy()
-            if "m" in slots:
-                out[tf_name + "/Adam"] = slots["m"][key].numpy().copy()
-            if "v" in slots:
-                out[tf_name + "/Adam_1"] = slots["v"][key].numpy().copy()
-            if "accum" in slots:
-                out[tf_name + "/Momentum"] = slots["accum"][key].numpy().copy()
+            for suffix, slot in _slot_suffixes(getattr(self, "opt", None)):
+                if slot in slots:
+                    out[tf_name + suffix] = slots[slot][key].numpy().copy()
         for k, v in powers.items():
             out[k] = np.array(v, dtype=np.float32)
         return out
@@ -113,7 +133,7 @@ class MnistRunnerBase:
         slots = {}
         for key, tf_name, _ in M.PARAM_SPECS:
             views[key].copy_(torch.from_numpy(np.asarray(tensors[tf_name])))
-            for suffix, slot in (("/Adam", "m"), ("/Adam_1", "v"), ("/Momentum", "accum")):
+            for suffix, slot in _slot_suffixes(getattr(self, "opt", None)):
                 if tf_name + suffix in tensors:
                     sflat = slots.setdefault(slot, torch.zeros(M.TOTAL))
                     M.dict_from_flat(sflat)[key].copy_(torch.from_numpy(np.asarray(tensors[tf_name + suffix])))
@@ -147,7 +167,8 @@ class TorchMnistRunner(MnistRunnerBase):
         self.opt = base_optimizer(optimizer)
         self.flat = torch.zeros(M.TOTAL, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros_like(self.flat)
-        self.applier = FlatApplier(self.opt, M.TOTAL, self.device)
+        segs = M.segments(self.opt.skip_bias) if is_layerwise(self.opt) else None
+        self.applier = FlatApplier(self.opt, M.TOTAL, self.device, segs)
         self._step = 0
         self.gen = torch.Generator(device=self.device).manual_seed(seed * 7919 + rank)
         self.comm = None  # DP reducer: callable(flat_grad) -> None (in-place average)
@@ -186,9 +207,13 @@ class TorchMnistRunner(MnistRunnerBase):
 
     def slot_tensors(self):
         s = self.applier.slots()
-        if self.opt.kind == "momentum":
+        if self.opt.kind in ("momentum", "lars"):
             return {"accum": s["m"]}
         return s
+
+    def last_layer_norms(self):
+        n = self.applier.last_layer_norms
+        return dict(zip(LAYER_NAMES, (tuple(float(x) for x in row) for row in n))) if n else {}
 
     def powers(self):
         return self.applier.powers()
@@ -276,6 +301,11 @@ class NativeMnistRunner(MnistRunnerBase):
         lr0 = lr_at(o.learning_rate, 0)
         if o.kind == "adam":
             self.eng.set_adam(lr0, o.beta1, o.beta2, o.epsilon)
+        elif o.kind == "lamb":
+            # per-variable norms and trust ratios formed on the device inside the step (csrc/layerwise.h)
+            self.eng.set_lamb(lr0, o.beta1, o.beta2, o.epsilon, o.weight_decay, bool(o.skip_bias))
+        elif o.kind == "lars":
+            self.eng.set_lars(lr0, o.momentum, o.weight_decay, o.eeta, o.epsilon, bool(o.skip_bias))
         elif o.kind == "momentum":
             self.eng.set_momentum(lr0, o.momentum, o.use_nesterov)
         else:
@@ -340,6 +370,13 @@ class NativeMnistRunner(MnistRunnerBase):
         self.stream.synchronize()
         norm, scale = self.eng.grad_norm().tolist()
         return float(norm), float(scale)
+
+    def last_layer_norms(self):
+        """A host read of the device table: call it only when something is logged."""
+        if not self.layerwise or self._hstep == 0:
+            return {}
+        self.stream.synchronize()
+        return dict(zip(LAYER_NAMES, (tuple(row) for row in self.eng.layer_norms().tolist())))
 
     # ---- device-resident input (reference feed: mnist_python_m.py:291-294) ----
     def set_device_dataset(self, images, labels, seed: int = 0) -> None:
@@ -424,9 +461,9 @@ class NativeMnistRunner(MnistRunnerBase):
 
     def slot_tensors(self):
         self.stream.synchronize()
-        if self.opt.kind == "adam":
+        if self.opt.kind in ("adam", "lamb"):
             return {"m": self.eng.adam_m(), "v": self.eng.adam_v()}
-        if self.opt.kind == "momentum":
+        if self.opt.kind in ("momentum", "lars"):
             return {"accum": self.eng.adam_m()}
         return {}
 

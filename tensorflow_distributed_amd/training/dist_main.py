@@ -100,8 +100,16 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("save_summaries_secs", 120.0, "Summary (global_step/sec) period (chief)")
     f.DEFINE_integer("seed", 0, "Init seed (normal(0,1) params, chief)")
     f.DEFINE_float("keep_prob", 0.75, "Dropout keep probability during training")
-    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum"], "Optimizer (reference: adam)")
-    f.DEFINE_float("momentum", 0.9, "Momentum for --optimizer=momentum")
+    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum", "lamb", "lars"], "Optimizer (reference: adam). lamb "
+                  "and lars scale every variable's update by a trust ratio formed from two per-variable L2 norms "
+                  "(on GPUs on the device, inside the step graph); synchronous all-reduce training of --model "
+                  "mnist_cnn only")
+    f.DEFINE_float("momentum", 0.9, "Momentum for --optimizer=momentum and lars")
+    f.DEFINE_float("weight_decay", -1.0, "--optimizer=lamb / lars: weight decay lambda (default: 0 for lamb, 1e-4 for "
+                   "lars)")
+    f.DEFINE_float("lars_eeta", 1e-3, "--optimizer=lars: the trust coefficient eeta")
+    f.DEFINE_boolean("layerwise_skip_bias", True, "--optimizer=lamb / lars: the biases take neither the weight decay "
+                     "nor the trust ratio (LARS's skip_list, LAMB's exclude_from_*)")
     f.DEFINE_boolean("synthetic_data", False, "Use the synthetic MNIST-shaped dataset even if IDX files exist")
     f.DEFINE_boolean("bf16_grads", True, "All-reduce gradients in bf16 (GPU)")
     f.DEFINE_boolean("use_graph", True, "Replay the captured hipGraph of the train step (GPU)")
@@ -183,16 +191,51 @@ def _make_learning_rate():
 
 
 def _make_optimizer():
-    from .optimizers import AdamOptimizer, GradientDescentOptimizer, MomentumOptimizer
+    from .optimizers import AdamOptimizer, GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer, MomentumOptimizer
 
     lr = _make_learning_rate()
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
     ema = dict(ema_decay=FLAGS.ema_decay, ema_num_updates=bool(FLAGS.ema_num_updates)) if FLAGS.ema_decay > 0 else {}
+    if FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
+        wd = {} if FLAGS.weight_decay < 0 else dict(weight_decay=FLAGS.weight_decay)
+        common = dict(skip_bias=bool(FLAGS.layerwise_skip_bias), clip_norm=clip, **wd, **ema)
+        if FLAGS.optimizer == "lamb":
+            return LAMBOptimizer(lr, **common)
+        return LARSOptimizer(lr, FLAGS.momentum, eeta=FLAGS.lars_eeta, **common)
     if FLAGS.optimizer == "sgd":
         return GradientDescentOptimizer(lr, clip_norm=clip, **ema)
     if FLAGS.optimizer == "momentum":
         return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip, **ema)
     return AdamOptimizer(lr, clip_norm=clip, **ema)
+
+
+LAYERWISE_OPTIMIZERS = ("lamb", "lars")
+
+
+def check_layerwise_flags(num_workers: int) -> None:
+    """--optimizer=lamb / lars form per-variable norms of the aggregated gradient of synchronous all-reduce
+    training. The combinations they do not cover are flag errors, raised before any process group is
+    built; each is a follow-up."""
+    if FLAGS.optimizer not in LAYERWISE_OPTIMIZERS:
+        if FLAGS.weight_decay >= 0:
+            raise ValueError("--weight_decay belongs to --optimizer=lamb / lars (got --optimizer=%s)" % FLAGS.optimizer)
+        return
+    which = "--optimizer=%s" % FLAGS.optimizer
+    if FLAGS.optimizer == "lars" and not FLAGS.lars_eeta > 0:
+        raise ValueError("--lars_eeta=%g: must be > 0" % FLAGS.lars_eeta)
+    if not FLAGS.sync_replicas:
+        raise ValueError("%s with --sync_replicas=False: the asynchronous parameter server applies each worker's "
+                         "gradient on its own shard, which has no per-variable norm (follow-up)" % which)
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("%s with backup workers (--replicas_to_aggregate=%d < %d workers): the accumulator paths "
+                         "have no layer-wise optimizer yet (follow-up)" % (which, r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the ResNet runner is not wired to the layer-wise ops yet "
+                         "(follow-up; the flat ops are general over the variable table)" % (which, FLAGS.model))
+    if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
+        raise ValueError("%s with --dp_schedule=%s: a sharded gradient has no per-variable norm; use the all-reduce "
+                         "schedule" % (which, FLAGS.dp_schedule))
 
 
 def check_clip_norm_flags(num_workers: int) -> None:
@@ -456,7 +499,8 @@ def dp_candidates(device_type: str, dtype: str):
     if device_type == "cuda":
         # --clip_norm: the global norm needs the whole aggregated gradient on every rank, which the
         # SFB / ZeRO schedules never form (MnistEngine.set_clip_norm)
-        if dtype != "bf16" or FLAGS.clip_norm > 0:
+        # --optimizer=lamb / lars: likewise for the per-variable norms (MnistEngine.set_lamb / set_lars)
+        if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
             return ["allreduce"]
         # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
         return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
@@ -579,6 +623,9 @@ def _choose_schedule(server, cluster, mnist, device, is_chief):
     if is_chief and device.type == "cuda" and FLAGS.clip_norm > 0:
         print("Worker %d: --clip_norm clips the all-reduced gradient: DP schedule candidates restricted to allreduce"
               % FLAGS.task_index)
+    if is_chief and device.type == "cuda" and FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
+        print("Worker %d: --optimizer=%s takes per-variable norms of the all-reduced gradient: DP schedule candidates "
+              "restricted to allreduce" % (FLAGS.task_index, FLAGS.optimizer))
     dp_sched, dp_probe, dp_source = choose_dp_schedule(run_one, FLAGS.task_index, num_workers, device.type, grp, log)
     if is_chief:
         print("Worker %d: DP schedule %s (%s%s)" % (
@@ -640,6 +687,7 @@ def main(argv=None) -> int:
         raise ValueError("Must specify an explicit `task_index`")
 
     check_clip_norm_flags(len(FLAGS.worker_hosts.split(",")))
+    check_layerwise_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
@@ -782,6 +830,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
             if FLAGS.clip_norm > 0:
                 rec["grad_norm"], rec["clip_scale"] = runner.last_grad_norm()
+            if FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
+                rec["trust_ratio"] = {k: v[2] for k, v in runner.last_layer_norms().items()}
             if opt.ema_decay:  # d_t of this step's update (host mirror)
                 rec["ema_decay"] = ema_decay_at(opt.ema_decay, step, opt.ema_num_updates)
             if phase_timing:

@@ -36,6 +36,14 @@ update ``e' = e - (1 - d_t)(e - p')`` with ``d_t = decay`` or, with ``num_update
 starts as a copy of the parameters. :func:`ema_decay_at` / :func:`ema_update` are the fp64 definition;
 the GPU optimizer kernels update the shadow themselves from ``p'`` in registers (``csrc/ema.h``,
 ``optim_ema.hip``, ``mnist_tail_ema.hip``).
+
+Layer-wise optimizers (``tf.contrib.opt.LARSOptimizer``; LAMB, You et al. / tensorflow_addons):
+:class:`LAMBOptimizer` and :class:`LARSOptimizer` scale every variable's update by a trust ratio formed
+from two L2 norms over that variable, and carry a weight decay. A variable has two flags, ``LW_DECAY``
+(the decay applies) and ``LW_ADAPT`` (the ratio applies); without them it uses ``lambda = 0`` and
+``r = 1``. :func:`trust_ratio`, :func:`lamb_update` and :func:`lars_update` are the fp64 definitions;
+the GPU forms the norms and the ratios on the device inside the step (``csrc/layerwise.h``,
+``csrc/kernels/optim_layerwise.hip``). ``t`` is ``global_step`` after the update; no beta powers exist.
 """
 from __future__ import annotations
 
@@ -266,6 +274,106 @@ class MomentumOptimizer:
         _check_ema(self.ema_decay)
 
 
+LW_DECAY, LW_ADAPT = 1, 2  # csrc/layerwise.h: LwFlags
+
+
+@dataclass
+class LAMBOptimizer:
+    """``u = c_t m' / (sqrt(v') + eps) + lambda p``; ``p' = p - lr r u``, ``r = |p| / |u|`` per variable.
+    With ``weight_decay`` and no variable adapted this is AdamW."""
+    learning_rate: LearningRate = 0.001
+    beta1: float = 0.9
+    beta2: float = 0.999
+    epsilon: float = 1e-6
+    weight_decay: float = 0.0
+    skip_bias: bool = True
+    clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+    name: str = "LAMB"
+    kind: str = field(default="lamb", init=False)
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
+        if self.weight_decay < 0:
+            raise ValueError(f"weight_decay must be >= 0, got {self.weight_decay!r}")
+
+
+@dataclass
+class LARSOptimizer:
+    """``accum' = mu accum + lr r (g + lambda p)``; ``p' = p - accum'``,
+    ``r = eeta |p| / (|g| + lambda |p| + eps)`` per variable (TF1 contrib: the rate is folded into the
+    accumulator). No Nesterov form."""
+    learning_rate: LearningRate = 0.01
+    momentum: float = 0.9
+    weight_decay: float = 1e-4
+    eeta: float = 1e-3
+    epsilon: float = 0.0
+    skip_bias: bool = True
+    clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+    name: str = "LARS"
+    kind: str = field(default="lars", init=False)
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
+        if self.weight_decay < 0 or not self.eeta > 0 or self.epsilon < 0:
+            raise ValueError("LARS: weight_decay >= 0, eeta > 0, epsilon >= 0")
+
+
+LAYERWISE_KINDS = ("lamb", "lars")
+
+
+def is_layerwise(opt) -> bool:
+    return getattr(base_optimizer(opt), "kind", None) in LAYERWISE_KINDS
+
+
+def trust_ratio(p_norm: float, x_norm: float, adapt: bool = True, eeta: Optional[float] = None,
+                weight_decay: float = 0.0, epsilon: float = 0.0) -> float:
+    """The trust ratio of one variable, fp64. LAMB (``eeta`` None): ``|p| / |u|`` with ``x_norm = |u|``.
+    LARS: ``eeta |p| / (|g| + lambda |p| + eps)`` with ``x_norm = |g|`` and ``weight_decay`` the
+    variable's effective ``lambda``. 1 for a variable that is not adapted or when either norm is 0."""
+    pn, xn = float(p_norm), float(x_norm)
+    if not (adapt and pn > 0.0 and xn > 0.0):
+        return 1.0
+    if eeta is None:
+        return pn / xn
+    return float(eeta) * pn / (xn + float(weight_decay) * pn + float(epsilon))
+
+
+def _norm64(x: torch.Tensor) -> float:
+    return math.sqrt(float(x.pow(2).sum().item()))
+
+
+def lamb_update(p, m, v, g, t: int, lr: float, beta1: float, beta2: float, epsilon: float, weight_decay: float = 0.0,
+                decay: bool = True, adapt: bool = True):
+    """One LAMB update of ONE variable in fp64: ``(p', m', v', (|p|, |u|, r))``. ``g`` is the gradient
+    the optimizer consumes (scale and clip factor applied), ``t`` the update's count (``global_step``
+    after it), ``lr`` the rate of this update."""
+    f = lambda x: x.detach().to(torch.float64)  # noqa: E731
+    p, m, v, g = f(p), f(m), f(v), f(g)
+    m2 = m + (g - m) * (1.0 - beta1)
+    v2 = v + (g * g - v) * (1.0 - beta2)
+    ct = math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    u = ct * m2 / (v2.sqrt() + epsilon) + (float(weight_decay) if decay else 0.0) * p
+    pn, un = _norm64(p), _norm64(u)
+    r = trust_ratio(pn, un, adapt)
+    return p - lr * r * u, m2, v2, (pn, un, r)
+
+
+def lars_update(p, accum, g, lr: float, momentum: float, weight_decay: float, eeta: float, epsilon: float = 0.0,
+                decay: bool = True, adapt: bool = True):
+    """One LARS update of ONE variable in fp64: ``(p', accum', (|p|, |g|, r))``."""
+    f = lambda x: x.detach().to(torch.float64)  # noqa: E731
+    p, accum, g = f(p), f(accum), f(g)
+    lam = float(weight_decay) if decay else 0.0
+    pn, gn = _norm64(p), _norm64(g)
+    r = trust_ratio(pn, gn, adapt, eeta, lam, epsilon)
+    a2 = momentum * accum + lr * r * (g + lam * p)
+    return p - a2, a2, (pn, gn, r)
+
+
 @dataclass
 class SyncReplicasOptimizer:
     """``tf.train.SyncReplicasOptimizer(opt, replicas_to_aggregate, total_num_replicas)``."""
@@ -315,6 +423,29 @@ def clip_by_global_norm(g: torch.Tensor, clip_norm: float, scale: float = 1.0) -
     return float(scale) * (c / (norm if norm > c else c)), norm
 
 
+def check_segments(segments, numel: int):
+    """The variable table as ``[(begin, length, flags)]`` of ints, checked as ``csrc/layerwise.h`` checks
+    it: sorted, disjoint, every begin a multiple of 4, any length >= 1, inside ``numel``; gaps allowed."""
+    out, end = [], 0
+    for i, (beg, n, flags) in enumerate(segments):
+        beg, n, flags = int(beg), int(n), int(flags)
+        if n < 1:
+            raise ValueError(f"segment {i} is empty (length >= 1)")
+        if beg < 0 or beg % 4:
+            raise ValueError(f"segment {i} does not begin on a multiple of 4")
+        if beg < end:
+            raise ValueError(f"segment {i} overlaps or precedes its predecessor (sorted, disjoint)")
+        if beg + n > numel:
+            raise ValueError(f"segment {i} ends outside the buffer")
+        if flags & ~(LW_DECAY | LW_ADAPT):
+            raise ValueError(f"segment {i} has unknown flags")
+        end = beg + n
+        out.append((beg, n, flags))
+    if not out:
+        raise ValueError("at least one segment")
+    return out
+
+
 def base_optimizer(opt):
     return opt.opt if isinstance(opt, SyncReplicasOptimizer) else opt
 
@@ -327,14 +458,22 @@ class FlatApplier:
     this shard, exactly like TF's per-PS ``beta1_power``).
     """
 
-    def __init__(self, opt, numel: int, device=None):
+    def __init__(self, opt, numel: int, device=None, segments=None):
         self.opt = base_optimizer(opt)
         self.device = device
         self.t = 0
         k = self.opt.kind
         z = lambda: torch.zeros(numel, dtype=torch.float32, device=device)  # noqa: E731
-        self.m = z() if k in ("adam", "momentum") else None
-        self.v = z() if k == "adam" else None
+        self.m = z() if k in ("adam", "momentum", "lamb", "lars") else None
+        self.v = z() if k in ("adam", "lamb") else None
+        # layer-wise optimizers: the variable table [(begin, length, flags)] (models.mnist_cnn.segments)
+        # and, after every apply(), [(|p|, |u| or |g|, r)] per variable
+        self.segments = None
+        self.last_layer_norms = None
+        if k in LAYERWISE_KINDS:
+            if segments is None:
+                raise ValueError(f"{self.opt.name}: a layer-wise optimizer needs the variable table (segments=...)")
+            self.segments = check_segments(segments, numel)
         self.last_grad_norm: Optional[float] = None  # norm / clip part of the last clipped apply()
         self.last_clip_scale: Optional[float] = None
         # moving average of the weights (ema_decay on the config): starts as a copy of the parameters at
@@ -359,6 +498,8 @@ class FlatApplier:
             self.m.add_(g - self.m, alpha=1 - b1)
             self.v.add_(g * g - self.v, alpha=1 - b2)
             p.sub_(lr_t * self.m / (self.v.sqrt() + o.epsilon))
+        elif o.kind in LAYERWISE_KINDS:
+            self._apply_layerwise(p, g, lr)
         elif o.kind == "momentum":
             self.m.mul_(o.momentum).add_(g)
             if o.use_nesterov:
@@ -371,6 +512,26 @@ class FlatApplier:
             # the update itself ran with EMA off or on alike; the shadow follows p' in fp32
             omd = 1.0 - ema_decay_at(o.ema_decay, self.t, o.ema_num_updates)
             self.ema.add_(p - self.ema, alpha=omd)
+
+    def _apply_layerwise(self, p: torch.Tensor, g: torch.Tensor, lr: float) -> None:
+        """Per variable, the fp64 definition; parameters and slots are stored in fp32. Elements that
+        belong to no variable are untouched."""
+        o = self.opt
+        norms = []
+        for beg, n, flags in self.segments:
+            sl = slice(beg, beg + n)
+            decay, adapt = bool(flags & LW_DECAY), bool(flags & LW_ADAPT)
+            if o.kind == "lamb":
+                p2, m2, v2, nr = lamb_update(p[sl], self.m[sl], self.v[sl], g[sl], self.t, lr, o.beta1, o.beta2, o.epsilon,
+                                             o.weight_decay, decay, adapt)
+                self.v[sl] = v2.to(torch.float32)
+            else:
+                p2, m2, nr = lars_update(p[sl], self.m[sl], g[sl], lr, o.momentum, o.weight_decay, o.eeta, o.epsilon,
+                                         decay, adapt)
+            self.m[sl] = m2.to(torch.float32)
+            p[sl] = p2.to(torch.float32)
+            norms.append(nr)
+        self.last_layer_norms = norms
 
     def reset_ema(self, p: torch.Tensor) -> None:
         """(Re)start the average as a copy of ``p`` (no zero-debias)."""

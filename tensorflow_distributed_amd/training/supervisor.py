@@ -109,6 +109,8 @@ class Supervisor:
         norm = self._global_norm()
         if norm is not None:
             vals.setdefault("global_norm", norm)
+        for var, row in self._layer_norms().items():
+            vals.setdefault("trust_ratio/" + var, row[2])
         if now > t0:
             vals["global_step/sec"] = (global_step - s0) / (now - t0)
         self.writer.add_scalars(vals, global_step)
@@ -123,6 +125,12 @@ class Supervisor:
         if lr is None:
             lr = getattr(self.runner, "learning_rate", None)
         return None if lr is None else lr_at(lr, global_step)
+
+    def _layer_norms(self) -> dict:
+        """The last update's per-variable trust ratios when the runner's optimizer is layer-wise (a host
+        read of the device table on GPUs: only here, when a summary is written)."""
+        read = getattr(self.runner, "last_layer_norms", None)
+        return read() if read is not None and getattr(self.runner, "layerwise", False) else {}
 
     def _global_norm(self) -> Optional[float]:
         """Norm of the last step's aggregated gradient when the runner clips by global norm (a host
