@@ -19,6 +19,9 @@
 //   fc_grad_sfb      DP: the fc gradients from all-gathered sufficient factors.
 // Each kernel's configuration constants won their A/B on one MI355X (logs: profiles/ab_*.log,
 // docs/DESIGN.md); losing arms and timing-only experiments are not kept in the source.
+// Inter-kernel outputs stored in 4-B or wider pieces by conv12_fwd_lds (p1, idx1), fc1_bwd and
+// conv2_bwd_lds are written through (csrc/wt_store.h, docs/DESIGN.md section 8b): no dirty L2 lines are
+// left for the end of the kernel to write back in front of its successor.
 #include "../common.h"
 
 #include "../gemm.h"
@@ -26,6 +29,7 @@
 #include "../launch_check.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
+#include "../wt_store.h"
 #include "../mnist_tail.h"
 
 #include <algorithm>
@@ -340,13 +344,14 @@ __global__ __launch_bounds__(512) void conv12_fwd_lds(MnistStepArgs a) {
   __syncthreads();
   if (nh == 0) {  // p1 / idx1 for the backward: 16-B stores from the LDS image and argmax array
     const uint8_t* idx_l = reinterpret_cast<const uint8_t*>(smem_raw + C12_IOFF);
-    for (int i = t; i < 196 * 4; i += 512) {
+    // written through (wt_store.h): the backward reads them three kernels later, on other XCDs
+    const WtBuf bp1 = wt_buf(a.p1 + (size_t)b * 196 * 32, 196 * 32 * 2), bi1 = wt_buf(a.idx1 + (size_t)b * 196 * 32, 196 * 32);
+    for (int i = t; i < 196 * 4; i += 512) {  // chunk i = (pixel pq, channel group cg) is bytes [16 i, 16 i + 16)
       const int pq = i >> 2, cg = i & 3, ph = pq / 14, pw = pq - ph * 14;
-      *reinterpret_cast<uint4*>(a.p1 + ((size_t)b * 196 + pq) * 32 + cg * 8) =
-          *reinterpret_cast<const uint4*>(img + (cg * C2F_PLANE + (ph + 2) * C2F_W + pw + 2) * 8);
+      wt_store16(bp1, (uint32_t)i * 16u, true,
+                 *reinterpret_cast<const uint4*>(img + (cg * C2F_PLANE + (ph + 2) * C2F_W + pw + 2) * 8));
     }
-    for (int i = t; i < 196 * 2; i += 512)
-      reinterpret_cast<uint4*>(a.idx1 + (size_t)b * 196 * 32)[i] = reinterpret_cast<const uint4*>(idx_l)[i];
+    for (int i = t; i < 196 * 2; i += 512) wt_store16(bi1, (uint32_t)i * 16u, true, reinterpret_cast<const uint4*>(idx_l)[i]);
   }
   C12_STAMP(4);
   // 5. conv2 implicit GEMM + bias + relu + pool + argmax (conv2_fwd_lds's main loop and epilogue)
@@ -388,6 +393,8 @@ __global__ __launch_bounds__(512) void conv12_fwd_lds(MnistStepArgs a) {
         const float z = acc[j][nt][r] + bb;
         if (z > mx) { mx = z; am = r; }
       }
+      // (2-B and 1-B stores: written through they would be one fabric write each; staged through LDS
+      // into 16-B chunks they measured +0.1 us plain, +0.2 written through -- docs/DESIGN.md section 8b)
       const size_t o = (size_t)b * FEAT + (m4 >> 2) * 64 + n;
       a.p2[o] = f2bf_bits(fmaxf(mx, 0.f));
       a.idx2[o] = (uint8_t)am;
@@ -577,18 +584,22 @@ __device__ __forceinline__ void out_grad_block(const MnistStepArgs& a, int blk, 
 #pragma unroll
   for (int c = 0; c < NCLS; ++c) part[(q * 64 + r) * NCLS + c] = acc[c];
   __syncthreads();
-  for (int i = t; i < OUTG_ROWS * NCLS; i += 256) {
-    const int rr = i / NCLS, mm = blk * OUTG_ROWS + rr;
-    if (mm <= HID) {
-      const size_t o = OFF_OUT + (size_t)mm * NCLS + (i - rr * NCLS);
-      const float g =
-          part[i] + part[OUTG_ROWS * NCLS + i] + part[2 * OUTG_ROWS * NCLS + i] + part[3 * OUTG_ROWS * NCLS + i];
-      if (a.gbf_a) {
-        a.gbf_a[o] = f2bf_bits(g);
-      } else {
-        a.grad[o] = g;
-      }
-    }
+  // The block's 64 rows x 10 classes are 640 contiguous outputs from OFF_OUT + 640 blk; rows past the
+  // bias row (the last block) are dropped by the store's range predicate. Written through
+  // (wt_store.h); bf16 as pairs in one 4-B store (10 is even: a pair never straddles the last row).
+  static_assert(OFF_OUT % 2 == 0 && NCLS % 2 == 0, "bf16 output-layer gradients are stored in pairs");
+  auto gsum = [&](int i) {
+    return part[i] + part[OUTG_ROWS * NCLS + i] + part[2 * OUTG_ROWS * NCLS + i] + part[3 * OUTG_ROWS * NCLS + i];
+  };
+  const int o0 = (int)OFF_OUT + blk * OUTG_ROWS * NCLS;
+  if (a.gbf_a) {
+    const WtBuf ob = wt_buf(a.gbf_a, TOTAL * 2);
+    for (int i = 2 * t; i < OUTG_ROWS * NCLS; i += 512)
+      wt_store4(ob, (uint32_t)(o0 + i) * 2u, blk * OUTG_ROWS + i / NCLS <= HID, pack_bf2(gsum(i), gsum(i + 1)));
+  } else {
+    const WtBuf ob = wt_buf(a.grad, TOTAL * 4);
+    for (int i = t; i < OUTG_ROWS * NCLS; i += 256)
+      wt_store4(ob, (uint32_t)(o0 + i) * 4u, blk * OUTG_ROWS + i / NCLS <= HID, __float_as_uint(gsum(i)));
   }
 }
 
@@ -629,16 +640,18 @@ __device__ __forceinline__ void fc1_dw_store(f32x4 (&acc)[2][2], float* cs, floa
 #pragma unroll
   for (int q = tid; q < FDW_BM * FDW_BN / 8; q += 256) {
     const int row = q >> 3, ch = q & 7, m = m0 + row;
-    if (m >= M) continue;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(cs + row * FDW_PITCH + ch * 8);
     const f32x4 hi = *reinterpret_cast<const f32x4*>(cs + row * FDW_PITCH + ch * 8 + 4);
-    const size_t o = (size_t)m * HID + n0 + ch * 8;
+    const uint32_t o = (uint32_t)(m * HID + n0 + ch * 8);
+    // written through (wt_store.h): the optimizer reads the gradient on other XCDs; rows past M (the
+    // last tile row) are dropped by the store's range predicate
     if (outbf) {
-      *reinterpret_cast<uint4*>(outbf + o) =
-          make_uint4(pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3]));
+      wt_store16(wt_buf(outbf, (int64_t)M * HID * 2), o * 2u, m < M,
+                 make_uint4(pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3])));
     } else {
-      *reinterpret_cast<f32x4*>(out + o) = lo;
-      *reinterpret_cast<f32x4*>(out + o + 4) = hi;
+      const WtBuf ob = wt_buf(out, (int64_t)M * HID * 4);
+      wt_store16(ob, o * 4u, m < M, f4_bits(lo));
+      wt_store16(ob, o * 4u + 16u, m < M, f4_bits(hi));
     }
   }
 }
@@ -706,7 +719,9 @@ __device__ __forceinline__ void fc1_dx_unpool_store(const MnistStepArgs& a, f32x
       o[q] = (i0 == (uint32_t)wi ? g[2 * q] : 0u) | (i1 == (uint32_t)wi ? g[2 * q + 1] << 16 : 0u);
     }
     const int oh = 2 * ph + (wi >> 1), ow = 2 * pwx + (wi & 1);
-    *reinterpret_cast<uint4*>(a.dz2 + ((size_t)(m * 14 + oh) * 14 + ow) * 64 + c0) = make_uint4(o[0], o[1], o[2], o[3]);
+    // written through (wt_store.h): conv2 backward stages dz2 on other XCDs
+    wt_store16(wt_buf(a.dz2, (int64_t)a.B * 196 * 64 * 2), (uint32_t)(((m * 14 + oh) * 14 + ow) * 64 + c0) * 2u, true,
+               make_uint4(o[0], o[1], o[2], o[3]));
   }
 }
 // fc1 dX tile width: 64 (196 blocks at B = 128) inside the fused fc backward, where the dX tiles
@@ -1167,7 +1182,7 @@ __device__ __forceinline__ void conv2_dgrad_body(const MnistStepArgs& a, const i
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int to = 16 * mi + 4 * g + r;  // taps 0..24, 25 = bias
-      if (to < 26) a.wg1_slab[(size_t)bid * 832 + to * 32 + c] = c2[r];
+      wt_store4(wt_buf(a.wg1_slab + (size_t)bid * 832, 832 * 4), (uint32_t)(to * 32 + c) * 4u, to < 26, __float_as_uint(c2[r]));
     }
     C2D_STAMP(7);
   }
@@ -1309,7 +1324,10 @@ __device__ __forceinline__ void conv2_wgrad_body(const MnistStepArgs& a, const i
   }
 #pragma unroll
   for (int j = 0; j < C2WL_MAXT; ++j) asm volatile("" : "+v"(acc[j][0]), "+v"(acc[j][1]));  // (as the dgrad's)
-  float* slab = a.wg2_slab + (size_t)ip * 801 * 64;
+  // the slab is written through (wt_store.h): the optimizer tail sums the slabs on other XCDs. 4-B stores
+  // in 64-B runs per 16-lane group; whole 256-B rows staged through LDS measured +0.5 us plain, +0.0
+  // written through (docs/DESIGN.md section 8b)
+  const WtBuf sb = wt_buf(a.wg2_slab + (size_t)ip * 801 * 64, 801 * 64 * 4);
 #pragma unroll
   for (int j = 0; j < C2WL_MAXT; ++j) {
     if (j < ntaps) {
@@ -1318,7 +1336,8 @@ __device__ __forceinline__ void conv2_wgrad_body(const MnistStepArgs& a, const i
       for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          slab[(size_t)(tap * 32 + 16 * h + 4 * g + r) * 64 + 16 * (n0 + u) + (lane & 15)] = acc[j][u][r];
+          wt_store4(sb, (uint32_t)((tap * 32 + 16 * h + 4 * g + r) * 64 + 16 * (n0 + u) + (lane & 15)) * 4u, true,
+                    __float_as_uint(acc[j][u][r]));
     }
   }
   if (tg == 0) {
@@ -1328,7 +1347,7 @@ __device__ __forceinline__ void conv2_wgrad_body(const MnistStepArgs& a, const i
       float sm = 0.f;
 #pragma unroll
       for (int sl = 0; sl < C2B_NT / 64; ++sl) sm += bred[sl * 64 + t];
-      slab[800 * 64 + t] = sm;
+      wt_store4(sb, (uint32_t)(800 * 64 + t) * 4u, true, __float_as_uint(sm));
     }
   }
   C2W_STAMP(7);
