@@ -4,6 +4,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include "../grad_accum.h"
 #include "../tfd_kernels.h"
 
 namespace tfd {
@@ -147,6 +148,40 @@ at::Tensor grad_global_norm(const at::Tensor& g, double clip_norm, double grad_s
   return out;
 }
 
+// Gradient accumulation over micro-batches (csrc/grad_accum.h), one flat pass: first (no out) acc = g;
+// no out: acc += g; out given: out = acc + g (acc untouched; out fp32 or bf16, and it may be g). g is
+// fp32 or bf16. blocks / loads: 0 = the kernel's defaults (grad_accum_tuned: the probe's A/B).
+void grad_accum_tuned(at::Tensor acc, const at::Tensor& g, c10::optional<at::Tensor> out, bool first, int64_t blocks,
+                      int64_t loads) {
+  const char* who = "grad_accum_flat";
+  const int64_t n = acc.numel();
+  TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.is_contiguous(), who, ": acc is a contiguous fp32 GPU tensor");
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && (gb || g.scalar_type() == at::kFloat) && g.is_contiguous(), who,
+              ": g is a contiguous fp32 or bf16 GPU tensor");
+  TORCH_CHECK(n >= 1 && g.numel() == n, who, ": acc and g hold the same number (>= 1) of elements, got ", n, " and ",
+              g.numel());
+  TORCH_CHECK(!(first && out), who, ": first (acc = g) takes no out");
+  const bool ob = out && out->scalar_type() == at::kBFloat16;
+  if (out)
+    TORCH_CHECK(out->is_cuda() && (ob || out->scalar_type() == at::kFloat) && out->is_contiguous() && out->numel() == n,
+                who, ": out is a contiguous fp32 or bf16 GPU tensor of acc's size");
+  TORCH_CHECK(blocks >= 0 && blocks <= 65536 && (loads == 0 || loads == 1 || loads == 2 || loads == 4), who,
+              ": blocks in [0, 65536], loads 0, 1, 2 or 4");
+  GradAccumArgs a{};
+  a.acc = (float*)acc.data_ptr();
+  a.g = gb ? nullptr : (const float*)g.data_ptr();
+  a.gbf = gb ? (const uint16_t*)g.data_ptr() : nullptr;
+  a.out = out && !ob ? (float*)out->data_ptr() : nullptr;
+  a.outbf = ob ? (uint16_t*)out->data_ptr() : nullptr;
+  a.n = n;
+  a.mode = out ? GA_EMIT : (first ? GA_STORE : GA_ADD);
+  grad_accum(a, cur(), (int)blocks, (int)loads);
+}
+void grad_accum_flat(at::Tensor acc, const at::Tensor& g, c10::optional<at::Tensor> out, bool first) {
+  grad_accum_tuned(acc, g, out, first, 0, 0);
+}
+
 void roofline_stream(at::Tensor p, at::Tensor m, at::Tensor v, const at::Tensor& g, at::Tensor pbf,
                      c10::optional<at::Tensor> x, int64_t blocks, int64_t unroll) {
   const int64_t n = p.numel();
@@ -204,6 +239,10 @@ TORCH_LIBRARY(tfd, m) {
   m.impl("ema_flat", c10::DispatchKey::CUDA, &ema_flat);
   m.def("grad_global_norm(Tensor g, float clip_norm, float grad_scale=1.0) -> Tensor");
   m.impl("grad_global_norm", c10::DispatchKey::CUDA, &grad_global_norm);
+  m.def("grad_accum_flat(Tensor(a!) acc, Tensor g, Tensor(b!)? out=None, bool first=False) -> ()");
+  m.impl("grad_accum_flat", c10::DispatchKey::CUDA, &grad_accum_flat);
+  m.def("grad_accum_tuned(Tensor(a!) acc, Tensor g, Tensor(b!)? out, bool first, int blocks, int loads) -> ()");
+  m.impl("grad_accum_tuned", c10::DispatchKey::CUDA, &grad_accum_tuned);
   m.def("roofline_stream(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!) pbf, Tensor? x, int blocks, "
         "int unroll) -> ()");
   m.impl("roofline_stream", c10::DispatchKey::CUDA, &roofline_stream);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../ema.h"
+#include "../grad_accum.h"
 #include "../layerwise_kernels.h"
 #include "../mnist_layout.h"
 #include "../tfd_kernels.h"
@@ -127,6 +128,44 @@ class MnistEngine : public torch::CustomClassHolder {
   at::Tensor feed_y() { return ybuf_; }
   int64_t batch() { return B_; }
   static int64_t max_batch() { return mnist_max_batch(); }
+
+  // Gradient accumulation: one train_step() is one optimizer step over K micro-batches of B rows
+  // (train_step_accum). K = 1 (the default) is off: the step is launch for launch what it was and
+  // nothing is allocated. K > 1 allocates, here and never inside a capture, the fp32 accumulator, the
+  // device micro-batch counter -- the data cursor, the prefetch tag and the dropout key of the
+  // micro-batch kernels, so micro-batch m trains on perm[(m * B + b) % n] and K of them are the rows of
+  // one batch of K * B -- and feed buffers of K * B rows (feed_x / feed_y: micro-batch j reads rows
+  // [j * B, (j + 1) * B); fetch them again after this call). Sets micro = K * global_step on the current
+  // stream; so must whoever writes step_tensor() afterwards (sync_micro_step). loss_rows() /
+  // correct_rows() hold the last micro-batch's values; the phase marks between the step's start and end
+  // are the last micro-batch's. Graphs captured before a call that changes K are dropped: they point
+  // at the buffers of the old K.
+  void set_grad_accum(int64_t K) {
+    TORCH_CHECK(K >= 1 && K <= 4096, "set_grad_accum: 1 <= K <= 4096, got ", K);
+    if (K != accum_) {
+      for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
+      graphs_.clear();
+    }
+    if (K > 1 && !acc_.defined()) {
+      acc_ = at::empty_like(grad_);  // stored whole by the first micro-batch of every step: never zero-filled
+      micro_ = at::zeros({1}, step_.options());
+    }
+    if (xbuf_.size(0) != K * B_ && (K > 1 || accum_ > 1)) {
+      xbuf_ = at::zeros({K * B_, 784}, xbuf_.options());
+      ybuf_ = at::zeros({K * B_}, ybuf_.options());
+    }
+    accum_ = K;
+    sync_micro_step();
+  }
+  int64_t grad_accum() const { return accum_; }
+  // the micro-batch counter (K = 1: the step counter itself is the cursor)
+  at::Tensor micro_step_tensor() { return micro_.defined() ? micro_ : step_; }
+  // micro = K * global_step, on the current stream: after every write of step_tensor()
+  void sync_micro_step() {
+    if (!micro_.defined()) return;
+    micro_.copy_(step_.mul(accum_));
+    invalidate_prefetch();
+  }
 
   void set_dataset(at::Tensor data, at::Tensor labels, at::Tensor perm) {
     TORCH_CHECK(data.is_cuda() && data.scalar_type() == at::kFloat && data.dim() == 2 && data.size(1) == 784,
@@ -472,6 +511,10 @@ class MnistEngine : public torch::CustomClassHolder {
     // each rank updates only its fc1 shard, so it would own only that shard of the averages
     TORCH_CHECK(!(ema_on() && zero_), "set_ema conflicts with ZeRO-1 (set_zero): each rank would hold only its fc1 "
                 "shard of the moving averages; use a schedule without ZeRO");
+    // the sharded schedules fuse gradient production with the collectives: no summed gradient to hold back
+    TORCH_CHECK(!(accum_ > 1 && (zero_ || sfb_active())), "set_grad_accum conflicts with ",
+                zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
+                ": the micro-batch gradients are summed whole before the one collective; use the all-reduce schedule");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -480,6 +523,10 @@ class MnistEngine : public torch::CustomClassHolder {
     const bool dp = this->dp();
     timed_ = timing_;
     timed_dp_ = timing_ && dp;
+    if (accum_ > 1) {
+      train_step_accum(dp);
+      return;
+    }
     if (clip_norm_ > 0 || lw_) {
       train_step_clip(dp);
       return;
@@ -823,25 +870,131 @@ class MnistEngine : public torch::CustomClassHolder {
         mark(P_BCONV, s);
       }
     }
+    whole_gradient_tail(bf, scale, s);
+  }
+
+  // The end of the steps that hold the whole aggregated gradient in one flat buffer (train_step_clip,
+  // train_step_accum) -- grad_, or gbf_ with a bf16 wire (bf) -- after the step bump: [clip: norm stage
+  // 1 -> norm stage 2] -> ONE optimizer over [0, TOTAL), t = global_step (layer-wise: its three stages).
+  void whole_gradient_tail(bool bf, double scale, hipStream_t s) {
+    const int64_t* step = (const int64_t*)step_.data_ptr();
     float* pair = (float*)gnorm_.data_ptr();
     float* part = (float*)gpart_.data_ptr();
+    const float* gscale = nullptr;  // the step's clip factor on the device; none without clipping
     if (clip_norm_ > 0) {
       grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
       grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
       tag("grad_norm", s);
+      gscale = pair + 1;
     }
     if (lw_) {
-      apply_layerwise(bf, scale, 0, step, clip_norm_ > 0 ? pair + 1 : nullptr, s);
+      apply_layerwise(bf, scale, 0, step, gscale, s);
     } else if (ema_on()) {
-      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
-      else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, pair + 1), s);
-    } else if (opt_ == 0) {
-      adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
+      else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
+    } else if (gscale) {
+      if (opt_ == 0) adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), gscale}, s);
+      else sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), gscale}, s);
     } else {
-      sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), pair + 1}, s);
+      if (opt_ == 0) adam_apply(adam_args(0, TOTAL, bf, scale, 0, step), s);
+      else sgd_apply(sgd_args(0, TOTAL, bf, scale, 0, step), s);
     }
     tag("opt", s);
     mark(P_OPT, s);
+  }
+
+  // One optimizer step over K = grad_accum() micro-batches (set_grad_accum), both dtypes, one GPU and
+  // the all-reduce DP schedule:
+  //   s: K x [forward -> fc backward -> conv backward -> conv-slab reduce (micro bump, next micro-batch's
+  //      gather) -> grad_accum over [0, TOTAL): store / add / emit] -> [DP: wait c] -> the tail of
+  //      train_step_clip (whole_gradient_tail) at scale 1 / (K * world)
+  //   c (DP): [wait the emit] ONE all-reduce per bucket, of the summed gradient
+  // The micro-batch kernels are those of the unfused path and write un-rounded fp32 into grad_ (per
+  // micro-batch rounding to bf16 is what accumulation must avoid); they read the micro counter where a
+  // plain step reads global_step (MnistStepArgs::step / step_bump), so the data cursor, the prefetch
+  // tag and the dropout key advance per micro-batch. The emit writes the sum where the collective or
+  // the optimizer reads it -- grad_, or bf16 into gbf_ with a bf16 wire -- and bumps global_step, which
+  // schedules, EMA decay and Adam's t follow.
+  void train_step_accum(bool dp) {
+    hipStream_t s = stream();
+    const int64_t K = accum_;
+    const double scale = 1.0 / (double)(K * world());
+    const bool bf = bf16_comm_ && dp;
+    int64_t* micro = (int64_t*)micro_.data_ptr();
+    if (pending_opt_a_) {  // an earlier DP graph left its fc-region optimizer running
+      wait(s, ev_opt_a_, "fc_fwd<-opt_fc");
+      pending_opt_a_ = false;
+    }
+    mark(P_START, s);
+    for (int64_t j = 0; j < K; ++j) {
+      const bool last = j == K - 1;
+      MnistStepArgs a = args();
+      a.step = micro;
+      a.step_bump = micro;
+      if (input_mode_ == 0) {  // fed: this micro-batch's rows of the K * B fed
+        a.data += j * B_ * 784;
+        a.labels += j * B_;
+      }
+      if (fp32_) {
+        MnistF32Args f = args_f32(a);
+        mnist_f32_forward(f, true, s);
+        tag("fwd", s);
+        if (last) mark(P_FWD, s);
+        mnist_f32_backward(f, s);
+        tag("bwd", s);
+        if (last) mark(P_BFC, s);
+        a.wg2_slab = f.wg2_slab;
+        a.wg2_splits = f.wg2_splits;
+        a.xpre = nullptr;  // as train_step_f32: no prefetch gather
+      } else {
+        mnist_forward_conv(a, s);
+        tag("conv_fwd", s);
+        mnist_forward_fc(a, true, s);
+        tag("fc_fwd", s);
+        if (last) mark(P_FWD, s);
+        mnist_backward_a(a, s, 0);
+        tag("fc_bwd", s);
+        if (last) mark(P_BFC, s);
+        mnist_backward_b(a, s);
+        tag("conv_bwd", s);
+      }
+      mnist_conv_grad_reduce(a, s);
+      tag("slab_reduce", s);
+      GradAccumArgs g{};
+      g.acc = (float*)acc_.data_ptr();
+      g.g = (const float*)grad_.data_ptr();
+      g.n = TOTAL;
+      g.mode = last ? GA_EMIT : (j == 0 ? GA_STORE : GA_ADD);
+      if (last) {
+        if (bf) g.outbf = (uint16_t*)gbf_.data_ptr();
+        else g.out = (float*)grad_.data_ptr();
+        g.bump = (int64_t*)step_.data_ptr();
+      }
+      tfd::grad_accum(g, s);
+      tag("accum", s);
+    }
+    if (!dp) {
+      mark(P_BCONV, s);
+    } else if (fp32_) {
+      mark(P_BCONV, s);
+      hand_off(s, ev_b_, comm_stream_, "ar<-accum");
+      mark(P_CA0, comm_stream_);
+      reduce_bucket(0, TOTAL, false);
+      tag("ar", comm_stream_);
+      mark(P_CA1, comm_stream_);
+      mark(P_CB0, comm_stream_);
+      mark(P_CB1, comm_stream_);
+      hand_off(comm_stream_, ev_done_, s, "grad_norm<-ar");
+    } else {
+      hand_off(s, ev_a_, comm_stream_, "ar_fc<-accum");
+      mark(P_CA0, comm_stream_);
+      reduce_bucket(BUCKET_SPLIT, TOTAL, bf);
+      tag("ar_fc", comm_stream_);
+      mark(P_CA1, comm_stream_);
+      all_reduce_conv(s, bf);  // behind bucket A's on the comm stream: ev_done_ covers both
+      wait(s, ev_done_, "grad_norm<-ar_conv");
+    }
+    whole_gradient_tail(bf, scale, s);
   }
 
   void train_step_zero() {
@@ -957,6 +1110,8 @@ class MnistEngine : public torch::CustomClassHolder {
   // compute part of a parameter-server worker step (the update runs on the PS task's GPU,
   // csrc/runtime/gpu_ps.cpp). Replayed with replay(name, 1) after the batch is fed.
   void capture_grads(const std::string& name) {
+    TORCH_CHECK(accum_ == 1, "capture_grads is one batch's forward and backward: set_grad_accum(1) first (grad_accum() = ",
+                accum_, ")");
     hipStream_t s = capture_stream();
     drop_graph(name);
     timed_ = false;
@@ -1346,9 +1501,10 @@ class MnistEngine : public torch::CustomClassHolder {
     }
   }
 
-  MnistF32Args args_f32() {
+  MnistF32Args args_f32() { return args_f32(args()); }
+  // the fp32 kernels' view of a step's arguments
+  MnistF32Args args_f32(const MnistStepArgs& a) {
     TORCH_CHECK(f1_.defined(), "set_dtype('fp32') first");
-    MnistStepArgs a = args();
     MnistF32Args f{};
     f.B = a.B;
     f.data = a.data;
@@ -1482,6 +1638,10 @@ class MnistEngine : public torch::CustomClassHolder {
   // global-norm clipping (set_clip_norm): 0 = off; {norm, scale} and stage 1's per-block partials
   double clip_norm_ = 0.0;
   at::Tensor gnorm_, gpart_;
+  // gradient accumulation (set_grad_accum): micro-batches per optimizer step (1 = off), the fp32
+  // accumulator and the device micro-batch counter
+  int64_t accum_ = 1;
+  at::Tensor acc_, micro_;
   // moving average of the weights (set_ema): 0 = off; the fp32 shadow, its bf16 image for
   // evaluate(use_ema) (cast when stale) and the device 1.0f the EMA variants read as their clip factor
   double ema_decay_ = 0.0;
@@ -1539,6 +1699,10 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("feed_x", &MnistEngine::feed_x)
       .def("feed_y", &MnistEngine::feed_y)
       .def("batch", &MnistEngine::batch)
+      .def("set_grad_accum", &MnistEngine::set_grad_accum)
+      .def("grad_accum", &MnistEngine::grad_accum)
+      .def("micro_step_tensor", &MnistEngine::micro_step_tensor)
+      .def("sync_micro_step", &MnistEngine::sync_micro_step)
       .def("set_dataset", &MnistEngine::set_dataset)
       .def("invalidate_prefetch", &MnistEngine::invalidate_prefetch)
       .def("set_debug_buffer", &MnistEngine::set_debug_buffer)

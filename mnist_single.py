@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --ema_decay --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -66,11 +66,17 @@ def main(argv=None):
     ap.add_argument("--ema_num_updates", type=int, default=1, help="--ema_decay: 1 = TF's num_updates=global_step, "
                     "the decay of update t is min(ema_decay, (1 + t) / (10 + t))")
     ap.add_argument("--ema_eval", type=int, default=1, help="--ema_decay: 1 = the final accuracy reads the averages")
+    ap.add_argument("--grad_accum_steps", type=int, default=1, help="gradient accumulation: every optimizer step sums "
+                    "this many micro-batches of --batch_size rows (GPU: on the device, inside the step graph); steps "
+                    "and Iter count optimizer steps of grad_accum_steps * batch_size images; 1 = off")
     ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
                     "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
     if a.ema_decay < 0 or a.ema_decay >= 1:
         ap.error("--ema_decay must be in (0, 1) (0 = off)")
+    if a.grad_accum_steps < 1:
+        ap.error("--grad_accum_steps must be >= 1 (1 = off)")
+    step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
     mnist = input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed)
@@ -78,7 +84,7 @@ def main(argv=None):
     ema = dict(ema_decay=a.ema_decay, ema_num_updates=bool(a.ema_num_updates)) if a.ema_decay > 0 else {}
     if a.optimizer == "adam" and a.weight_decay >= 0:
         ap.error("--weight_decay belongs to --optimizer lamb / lars")
-    common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, **ema)
+    common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, accum_steps=a.grad_accum_steps, **ema)
     if a.optimizer != "adam":
         common.update(skip_bias=bool(a.layerwise_skip_bias), **({} if a.weight_decay < 0 else dict(weight_decay=a.weight_decay)))
     if a.optimizer == "lamb":
@@ -104,11 +110,11 @@ def main(argv=None):
     step = 1
     if train_flag == 1:
         # Keep training until reach max iterations
-        while step * a.batch_size < a.training_iters:
+        while step * step_rows < a.training_iters:
             if device_input:
                 runner.train_step(None, None)  # next_batch happens on the device
             else:
-                batch_x, batch_y = mnist.train.next_batch(a.batch_size)
+                batch_x, batch_y = mnist.train.next_batch(step_rows)
                 # Run optimization op (backprop)
                 runner.train_step(batch_x, batch_y)
             if step % a.display_step == 0:
@@ -117,11 +123,14 @@ def main(argv=None):
                 # Calculate batch loss (keep_prob = 1)
                 loss_sum, _ = runner.evaluate(batch_x, batch_y)
                 loss = loss_sum / len(batch_x)
-                print("Iter " + str(step * a.batch_size) + ", Minibatch Loss= " + "{:.6f}".format(loss))
+                print("Iter " + str(step * step_rows) + ", Minibatch Loss= " + "{:.6f}".format(loss))
             step += 1
         print("Optimization Finished!")
         training_end_time = time.time()
         print("--- %s seconds Time for Training ---" % (training_end_time - start_time))
+        if a.grad_accum_steps > 1:
+            print("%d optimizer steps of %d micro-batches x %d images: %.1f images/sec" % (
+                step - 1, a.grad_accum_steps, a.batch_size, (step - 1) * step_rows / max(training_end_time - start_time, 1e-9)))
         if a.logdir:
             print("Saved %s" % saver.save(a.logdir, runner.state_dict_tf(), global_step=runner.global_step()))
     else:

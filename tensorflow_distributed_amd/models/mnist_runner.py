@@ -165,6 +165,7 @@ class TorchMnistRunner(MnistRunnerBase):
         self.device = device or torch.device("cpu")
         self.keep_prob = keep_prob
         self.opt = base_optimizer(optimizer)
+        self.accum_steps = int(getattr(self.opt, "accum_steps", 1))  # micro-batches of batch_size per update
         self.flat = torch.zeros(M.TOTAL, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros_like(self.flat)
         segs = M.segments(self.opt.skip_bias) if is_layerwise(self.opt) else None
@@ -245,10 +246,26 @@ class TorchMnistRunner(MnistRunnerBase):
         self._step += 1
 
     def train_step(self, x, y) -> None:
-        g, _ = self.compute_grads(x, y)
+        """One update from ``accum_steps * batch_size`` rows: the micro-batches' gradients, each with its
+        own dropout mask drawn in order, are summed in fp32 as the device sums them, reduced once and
+        applied once at scale ``1 / accum_steps``. The loss is the last micro-batch's."""
+        K, B = self.accum_steps, self.batch_size
+        if K == 1:
+            g, _ = self.compute_grads(x, y)
+            if self.comm is not None:
+                self.comm(g)
+            self.apply_grads(g)
+            return
+        x, y = _as_f32(x), _labels_to_ids(y)
+        assert x.shape[0] == K * B, f"{x.shape[0]} rows != accum_steps {K} x batch {B}"
+        acc = None
+        for j in range(K):
+            g, _ = self.compute_grads(x[j * B:(j + 1) * B], y[j * B:(j + 1) * B])
+            acc = g.clone() if acc is None else acc.add_(g)
+        self.grad.copy_(acc)
         if self.comm is not None:
-            self.comm(g)
-        self.apply_grads(g)
+            self.comm(self.grad)
+        self.apply_grads(self.grad, 1.0 / K)
 
     def last_loss(self) -> float:
         return float(getattr(self, "_last_loss", float("nan")))
@@ -324,11 +341,18 @@ class NativeMnistRunner(MnistRunnerBase):
             # the optimizer kernels update the shadow themselves from p' in registers (csrc/ema.h)
             with torch.cuda.stream(self.stream):
                 self.eng.set_ema(float(o.ema_decay), bool(o.ema_num_updates))
+        # gradient accumulation: one train_step is accum_steps micro-batches of batch_size rows, summed on
+        # the device (csrc/kernels/grad_accum.hip); the engine's micro counter is accum_steps * global_step
+        # at every step boundary, which is all the host needs to mirror it
+        self.accum_steps = int(getattr(o, "accum_steps", 1))
+        if self.accum_steps > 1:
+            with torch.cuda.stream(self.stream):
+                self.eng.set_grad_accum(self.accum_steps)
         self.use_graph = use_graph
         self._graph_ready = False
         self._grads_graph = False
-        self._x_stage = torch.empty(batch_size, 784, dtype=torch.float32).pin_memory()
-        self._y_stage = torch.empty(batch_size, dtype=torch.int32).pin_memory()
+        self._x_stage = torch.empty(self.accum_steps * batch_size, 784, dtype=torch.float32).pin_memory()
+        self._y_stage = torch.empty(self.accum_steps * batch_size, dtype=torch.int32).pin_memory()
         self.transport = None  # parallel.transport.DPTransport when DP runs over RCCL/IPC
         self._dev_data = None  # device-resident split (set_device_dataset)
         self._hstep = 0        # host mirror of the device global_step (epoch bookkeeping, no sync)
@@ -382,7 +406,10 @@ class NativeMnistRunner(MnistRunnerBase):
     def set_device_dataset(self, images, labels, seed: int = 0) -> None:
         """Upload a training split once; every later ``train_step(None, None)`` gathers its batch on
         the device from ``perm[(global_step * B + b) % n]``. The permutation is redrawn at every
-        epoch boundary, which is ``DataSet.next_batch``'s per-epoch reshuffle without a host feed."""
+        epoch boundary, which is ``DataSet.next_batch``'s per-epoch reshuffle without a host feed.
+        With ``accum_steps = K`` micro-batch ``m = K * global_step + j`` gathers ``perm[(m * B + b) % n]``:
+        a step trains on ``K * B`` consecutive positions, and the reshuffle happens at the first step
+        boundary after an epoch ends."""
         x = _as_f32(images)
         y = _labels_to_ids(labels)
         n = x.shape[0]
@@ -395,12 +422,18 @@ class NativeMnistRunner(MnistRunnerBase):
             self.eng.set_input_mode(1)
         self.stream.synchronize()
         self._hstep = self.global_step()
-        self._epoch = (self._hstep * self.batch_size) // n
+        self._epoch = (self._hstep * self._step_rows) // n
+
+    @property
+    def _step_rows(self) -> int:
+        """Rows one train_step consumes: ``accum_steps`` micro-batches of ``batch_size``."""
+        return self.accum_steps * self.batch_size
 
     def last_device_batch(self):
-        """(x, y) device tensors of the batch the last device-input step trained on."""
+        """(x, y) device tensors of the rows the last device-input step trained on (``accum_steps *
+        batch_size`` of them, in micro-batch order)."""
         n = self._dev_data.shape[0]
-        pos = ((self._hstep - 1) * self.batch_size + torch.arange(self.batch_size, device=self.device)) % n
+        pos = ((self._hstep - 1) * self._step_rows + torch.arange(self._step_rows, device=self.device)) % n
         with torch.cuda.stream(self.stream):
             rows = self._dev_perm[pos].long()
             out = self._dev_data[rows], self._dev_labels[rows]
@@ -409,7 +442,7 @@ class NativeMnistRunner(MnistRunnerBase):
 
     def _device_batch(self) -> None:
         n = self._dev_data.shape[0]
-        ep = (self._hstep * self.batch_size) // n
+        ep = (self._hstep * self._step_rows) // n
         if ep != self._epoch:
             self._epoch = ep
             p = torch.randperm(n, generator=self._perm_gen).to(torch.int32)
@@ -428,6 +461,7 @@ class NativeMnistRunner(MnistRunnerBase):
     def set_global_step(self, s: int) -> None:
         with torch.cuda.stream(self.stream):
             self.eng.step_tensor().fill_(int(s))
+            self.eng.sync_micro_step()  # micro = accum_steps * global_step
         self._hstep = int(s)
 
     def load_flat(self, flat, slots, step):
@@ -439,6 +473,7 @@ class NativeMnistRunner(MnistRunnerBase):
             if "v" in slots:
                 self.eng.adam_v().copy_(slots["v"].to(self.device))
             self.eng.step_tensor().fill_(int(step))
+            self.eng.sync_micro_step()
             if self.ema_on:
                 self.eng.load_ema(self.eng.params())
         self.stream.synchronize()
@@ -490,6 +525,7 @@ class NativeMnistRunner(MnistRunnerBase):
             self.comm.broadcast(self.eng.adam_m(), root)
             self.comm.broadcast(self.eng.adam_v(), root)
             self.comm.broadcast(self.eng.step_tensor(), root)
+            self.eng.sync_micro_step()
             if self.ema_on:
                 self.comm.broadcast(self.eng.ema_params(), root)
             self.eng.sync_shadow()
@@ -506,7 +542,8 @@ class NativeMnistRunner(MnistRunnerBase):
             raise ValueError("host batches fed to a runner in device-input mode")
         x = _as_f32(x)
         y = _labels_to_ids(y)
-        assert x.shape[0] == self.batch_size, f"batch {x.shape[0]} != engine batch {self.batch_size}"
+        assert x.shape[0] == self._step_rows, \
+            f"batch {x.shape[0]} != accum_steps {self.accum_steps} x engine batch {self.batch_size}"
         self._x_stage.copy_(x)
         self._y_stage.copy_(y)
         with torch.cuda.stream(self.stream):
@@ -534,7 +571,10 @@ class NativeMnistRunner(MnistRunnerBase):
     def compute_grads(self, x, y, with_loss: bool = True) -> Tuple[torch.Tensor, Optional[float]]:
         """Forward + backward only (no reduction / optimizer). Bumps the engine's local step. With
         ``use_graph`` the three launches replay as one captured graph (``MnistEngine.capture_grads``).
-        ``with_loss=False`` skips the loss read-back (no device-to-host transfer)."""
+        ``with_loss=False`` skips the loss read-back (no device-to-host transfer). One batch only: with
+        ``accum_steps > 1`` it raises (the parameter-server modes that use it do not accumulate)."""
+        if self.accum_steps > 1:
+            raise ValueError(f"compute_grads handles one batch; the optimizer has accum_steps={self.accum_steps}")
         self._feed(x, y)
         with torch.cuda.stream(self.stream):
             if self.use_graph:

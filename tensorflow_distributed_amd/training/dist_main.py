@@ -84,6 +84,11 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "min(ema_decay, (1 + t) / (10 + t))")
     f.DEFINE_boolean("ema_eval", True, "--ema_decay: --eval_at_steps, the validation prints and the final accuracy "
                      "read the averages instead of the variables")
+    f.DEFINE_integer("grad_accum_steps", 1, "Gradient accumulation: every optimizer step sums this many micro-batches "
+                     "of --batch_size rows per worker (on GPUs on the device, inside the step graph) before the one "
+                     "clip, trust ratio, all-reduce and update. --train_steps, global_step/sec, checkpoints and "
+                     "--eval_at_steps count optimizer steps. 1 = off. Synchronous all-reduce training of --model "
+                     "mnist_cnn only")
     f.DEFINE_boolean("sync_replicas", True, "Use the sync_replicas (synchronized replicas) mode, "
                      "wherein the parameter updates from workers are aggregated before applied to "
                      "avoid stale gradients")
@@ -195,18 +200,19 @@ def _make_optimizer():
 
     lr = _make_learning_rate()
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
+    acc = int(FLAGS.grad_accum_steps)
     ema = dict(ema_decay=FLAGS.ema_decay, ema_num_updates=bool(FLAGS.ema_num_updates)) if FLAGS.ema_decay > 0 else {}
     if FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
         wd = {} if FLAGS.weight_decay < 0 else dict(weight_decay=FLAGS.weight_decay)
         common = dict(skip_bias=bool(FLAGS.layerwise_skip_bias), clip_norm=clip, **wd, **ema)
         if FLAGS.optimizer == "lamb":
-            return LAMBOptimizer(lr, **common)
-        return LARSOptimizer(lr, FLAGS.momentum, eeta=FLAGS.lars_eeta, **common)
+            return LAMBOptimizer(lr, accum_steps=acc, **common)
+        return LARSOptimizer(lr, FLAGS.momentum, eeta=FLAGS.lars_eeta, accum_steps=acc, **common)
     if FLAGS.optimizer == "sgd":
-        return GradientDescentOptimizer(lr, clip_norm=clip, **ema)
+        return GradientDescentOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
     if FLAGS.optimizer == "momentum":
-        return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip, **ema)
-    return AdamOptimizer(lr, clip_norm=clip, **ema)
+        return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip, accum_steps=acc, **ema)
+    return AdamOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
 
 
 LAYERWISE_OPTIMIZERS = ("lamb", "lars")
@@ -236,6 +242,31 @@ def check_layerwise_flags(num_workers: int) -> None:
     if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
         raise ValueError("%s with --dp_schedule=%s: a sharded gradient has no per-variable norm; use the all-reduce "
                          "schedule" % (which, FLAGS.dp_schedule))
+
+
+def check_grad_accum_flags(num_workers: int) -> None:
+    """--grad_accum_steps sums micro-batch gradients ahead of the one aggregated update of synchronous
+    all-reduce training. The combinations it does not cover are flag errors, raised before any process
+    group is built (every rank sees the same flags), not silently unaccumulated runs."""
+    k = FLAGS.grad_accum_steps
+    if k < 1:
+        raise ValueError("--grad_accum_steps=%d: must be >= 1 (1 = off)" % k)
+    if k == 1:
+        return
+    which = "--grad_accum_steps=%d" % k
+    if not FLAGS.sync_replicas:
+        raise ValueError("%s with --sync_replicas=False: the asynchronous parameter server applies each worker's "
+                         "gradient as it arrives; there is no update to accumulate towards" % which)
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("%s with backup workers (--replicas_to_aggregate=%d < %d workers): the accumulator paths "
+                         "take one batch per worker and step" % (which, r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the ResNet runner does not accumulate" % (which, FLAGS.model))
+    if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
+        raise ValueError("%s with --dp_schedule=%s: the SFB / ZeRO schedules fuse gradient production with their "
+                         "collectives, so there is no whole gradient to sum; use the all-reduce schedule"
+                         % (which, FLAGS.dp_schedule))
 
 
 def check_clip_norm_flags(num_workers: int) -> None:
@@ -500,7 +531,10 @@ def dp_candidates(device_type: str, dtype: str):
         # --clip_norm: the global norm needs the whole aggregated gradient on every rank, which the
         # SFB / ZeRO schedules never form (MnistEngine.set_clip_norm)
         # --optimizer=lamb / lars: likewise for the per-variable norms (MnistEngine.set_lamb / set_lars)
-        if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
+        # --grad_accum_steps: the micro-batch gradients are summed whole before the one collective
+        # (MnistEngine.set_grad_accum)
+        if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS or \
+                FLAGS.grad_accum_steps > 1:
             return ["allreduce"]
         # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
         return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
@@ -592,8 +626,9 @@ def _probe_cpu_schedule(name, num_workers, group):
         r.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0)
         r.comm = GlooGradAverager(group, num_workers, [M.BUCKET_SPLIT] if name == "buckets" else None)
         g = torch.Generator().manual_seed(FLAGS.task_index + 5)
-        x = torch.rand(FLAGS.batch_size, 784, generator=g)
-        y = torch.randint(0, 10, (FLAGS.batch_size,), generator=g)
+        rows = FLAGS.batch_size * FLAGS.grad_accum_steps  # one step's rows
+        x = torch.rand(rows, 784, generator=g)
+        y = torch.randint(0, 10, (rows,), generator=g)
 
     def timed():
         n = max(1, min(FLAGS.dp_probe_steps, 5))
@@ -687,6 +722,7 @@ def main(argv=None) -> int:
         raise ValueError("Must specify an explicit `task_index`")
 
     check_clip_norm_flags(len(FLAGS.worker_hosts.split(",")))
+    check_grad_accum_flags(len(FLAGS.worker_hosts.split(",")))
     check_layerwise_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
 
@@ -800,6 +836,14 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
             FLAGS.task_index, opt.ema_decay, " (num_updates = global_step)" if opt.ema_num_updates else "",
             "averages" if ema_eval else "variables"))
 
+    # --grad_accum_steps: --batch_size stays the micro-batch (the engine batch); a step draws accum of them
+    accum = int(getattr(opt, "accum_steps", 1))
+    step_rows = FLAGS.batch_size * accum
+    if is_chief and accum > 1:
+        print("Worker %d: gradient accumulation, %d micro-batches of %d per optimizer step: %d images per step over "
+              "%d worker(s); steps are optimizer steps" % (FLAGS.task_index, accum, FLAGS.batch_size,
+                                                          step_rows * (num_workers if sync else 1), num_workers))
+
     def eval_batch():
         val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
         return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
@@ -812,7 +856,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
             if device_input:
                 batch_xs = batch_ys = None  # the engine gathers the batch on the device
             else:
-                batch_xs, batch_ys = mnist.train.next_batch(FLAGS.batch_size)
+                batch_xs, batch_ys = mnist.train.next_batch(step_rows)
         t0 = time.time()
         with timer.phase("step"), trace_range("train_step"):
             step = gsync.step(batch_xs, batch_ys, step)
@@ -825,7 +869,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 print("Worker %d: stale gradient dropped (a backup replica finished this step first)" % FLAGS.task_index)
         if metrics.path:
             rec = dict(step=local_step, global_step=step, step_ms=1e3 * (now - t0), loss=runner.last_loss(),
-                       images_per_sec=FLAGS.batch_size * (num_workers if sync else 1) / max(now - t0, 1e-9))
+                       images_per_sec=step_rows * (num_workers if sync else 1) / max(now - t0, 1e-9),
+                       accum_steps=accum)
             if gsync.logs_lr:
                 rec["lr"] = lr_at(learning_rate, max(step - 1, 0))
             if FLAGS.clip_norm > 0:
@@ -880,6 +925,9 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     if transport is not None:
         transport.check("training")  # a timed-out IPC barrier must not pass as a finished run
     training_time = _training_ends(time_begin, eval_time)
+    print("Worker %d: %.1f images/sec (%d optimizer steps of %d images)" % (
+        FLAGS.task_index, step_rows * (num_workers if sync else 1) * local_step / max(training_time, 1e-9), local_step,
+        step_rows * (num_workers if sync else 1)))
     mean_accuracy = _validate(eval_batch)
     metrics.log(event="final", global_step=step, training_time_s=training_time, mean_accuracy=mean_accuracy)
     if perf_rows:

@@ -50,7 +50,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Optional, Tuple, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -241,9 +241,11 @@ class AdamOptimizer:
     clip_norm: Optional[float] = None
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
 
 
 @dataclass
@@ -254,9 +256,11 @@ class GradientDescentOptimizer:
     clip_norm: Optional[float] = None
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
 
 
 @dataclass
@@ -269,9 +273,11 @@ class MomentumOptimizer:
     clip_norm: Optional[float] = None
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
 
 
 LW_DECAY, LW_ADAPT = 1, 2  # csrc/layerwise.h: LwFlags
@@ -290,11 +296,13 @@ class LAMBOptimizer:
     clip_norm: Optional[float] = None
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
     name: str = "LAMB"
     kind: str = field(default="lamb", init=False)
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
         if self.weight_decay < 0:
             raise ValueError(f"weight_decay must be >= 0, got {self.weight_decay!r}")
 
@@ -313,11 +321,13 @@ class LARSOptimizer:
     clip_norm: Optional[float] = None
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
     name: str = "LARS"
     kind: str = field(default="lars", init=False)
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
         if self.weight_decay < 0 or not self.eeta > 0 or self.epsilon < 0:
             raise ValueError("LARS: weight_decay >= 0, eeta > 0, epsilon >= 0")
 
@@ -403,6 +413,25 @@ class SyncReplicasOptimizer:
     def has_backup_workers(self) -> bool:
         return self.replicas_to_aggregate is not None and self.total_num_replicas is not None and \
             self.replicas_to_aggregate < self.total_num_replicas
+
+
+def _check_accum(k) -> None:
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accum_steps must be an integer >= 1, got {k!r}")
+
+
+def accumulate_gradients(grads: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Gradient accumulation's definition in fp64: the micro-batch gradients summed one after another in
+    the order given, unscaled (the optimizer takes the sum at scale ``1 / (K * world)``). The device does
+    the same sum in fp32 (``csrc/kernels/grad_accum.hip``)."""
+    if len(grads) < 1:
+        raise ValueError("accumulate_gradients: at least one gradient")
+    acc = grads[0].detach().to(torch.float64).clone()
+    for g in grads[1:]:
+        if g.shape != acc.shape:
+            raise ValueError("accumulate_gradients: gradients of one shape")
+        acc += g.detach().to(torch.float64)
+    return acc
 
 
 def clip_by_global_norm(g: torch.Tensor, clip_norm: float, scale: float = 1.0) -> Tuple[float, float]:
