@@ -28,6 +28,12 @@ const float* clip_factor(const at::Tensor& t, const char* who) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == 1, who, ": gscale is one fp32 GPU element");
   return (const float*)t.data_ptr();
 }
+// guard: the non-finite guard's device ok, the [3] result of grad_guard or a one-element view of its ok
+const float* guard_ok(const at::Tensor& t, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && (t.numel() == 3 || t.numel() == 1), who,
+              ": guard is grad_guard's fp32 GPU [3] result or its ok element");
+  return (const float*)t.data_ptr() + (t.numel() == 3 ? 2 : 0);
+}
 float* ema_shadow(const at::Tensor& e, const at::Tensor& p, double decay, const char* who) {
   TORCH_CHECK(e.is_cuda() && e.scalar_type() == at::kFloat && e.is_contiguous() && e.numel() == p.numel(), who,
               ": ema is a contiguous fp32 GPU tensor of p's size");
@@ -91,7 +97,8 @@ void layerwise_plan_args(LayerwiseArgs& a, const LayerwisePlan& pl) {
 LayerwiseArgs layerwise_args(const char* who, at::Tensor& p, at::Tensor& s1, const at::Tensor& g,
                              const c10::optional<at::Tensor>& pbf, const c10::optional<at::Tensor>& step, int64_t t_offset,
                              double grad_scale, const LrSchedule& sc, const c10::optional<at::Tensor>& gscale,
-                             const c10::optional<at::Tensor>& ema, double ema_decay, bool ema_num_updates) {
+                             const c10::optional<at::Tensor>& ema, double ema_decay, bool ema_num_updates,
+                             const c10::optional<at::Tensor>& guard) {
   const int64_t n = p.numel();
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
   TORCH_CHECK(s1.is_cuda() && s1.scalar_type() == at::kFloat && s1.is_contiguous() && s1.numel() == n, who,
@@ -120,19 +127,23 @@ LayerwiseArgs layerwise_args(const char* who, at::Tensor& p, at::Tensor& s1, con
     a.ema_decay = (float)ema_decay;
     a.ema_num_updates = ema_num_updates ? 1 : 0;
   }
+  if (guard) a.ok = guard_ok(*guard, who);
   return a;
 }
 
-// LAMB over the variables of `segs`; returns [S,3] = {|p|, |u|, r} per variable (fp32, on the device)
+// LAMB over the variables of `segs`; returns [S,3] = {|p|, |u|, r} per variable (fp32, on the device).
+// guard (here and in lars_flat): with its ok == 0 nothing is stored to p, the slots, pbf or ema, and the
+// [S,3] result is unspecified.
 at::Tensor lamb_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf, at::Tensor segs,
                      double lr, double b1, double b2, double eps, double weight_decay, c10::optional<at::Tensor> step,
                      int64_t t_offset, double grad_scale, std::string lr_kind, std::vector<double> lr_params,
                      std::vector<int64_t> lr_boundaries, std::vector<double> lr_values, c10::optional<at::Tensor> gscale,
-                     c10::optional<at::Tensor> ema, double ema_decay, bool ema_num_updates) {
+                     c10::optional<at::Tensor> ema, double ema_decay, bool ema_num_updates,
+                     c10::optional<at::Tensor> guard) {
   const char* who = "lamb_flat";
   LayerwiseArgs a = layerwise_args(who, p, m, g, pbf, step, t_offset, grad_scale,
                                    flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), gscale, ema, ema_decay,
-                                   ema_num_updates);
+                                   ema_num_updates, guard);
   TORCH_CHECK(v.is_cuda() && v.scalar_type() == at::kFloat && v.is_contiguous() && v.numel() == p.numel(), who,
               ": slots are contiguous fp32 GPU tensors of p's size");
   const LayerwisePlan pl = layerwise_plan(segs, p.numel(), p, who);
@@ -151,11 +162,12 @@ at::Tensor lars_flat(at::Tensor p, at::Tensor accum, at::Tensor g, c10::optional
                      double momentum, double weight_decay, double eeta, double eps, c10::optional<at::Tensor> step,
                      int64_t t_offset, double grad_scale, std::string lr_kind, std::vector<double> lr_params,
                      std::vector<int64_t> lr_boundaries, std::vector<double> lr_values, c10::optional<at::Tensor> gscale,
-                     c10::optional<at::Tensor> ema, double ema_decay, bool ema_num_updates) {
+                     c10::optional<at::Tensor> ema, double ema_decay, bool ema_num_updates,
+                     c10::optional<at::Tensor> guard) {
   const char* who = "lars_flat";
   LayerwiseArgs a = layerwise_args(who, p, accum, g, pbf, step, t_offset, grad_scale,
                                    flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), gscale, ema, ema_decay,
-                                   ema_num_updates);
+                                   ema_num_updates, guard);
   const LayerwisePlan pl = layerwise_plan(segs, p.numel(), p, who);
   layerwise_plan_args(a, pl);
   a.momentum = (float)momentum;
@@ -187,12 +199,14 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
   m.def("lamb_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, Tensor segs, float lr, float beta1, "
         "float beta2, float eps, float weight_decay, Tensor? step=None, int t_offset=1, float grad_scale=1.0, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
-        "Tensor? gscale=None, Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False) -> Tensor");
+        "Tensor? gscale=None, Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False, "
+        "Tensor? guard=None) -> Tensor");
   m.impl("lamb_flat", c10::DispatchKey::CUDA, &lamb_flat);
   m.def("lars_flat(Tensor(a!) p, Tensor(b!) accum, Tensor g, Tensor(d!)? pbf, Tensor segs, float lr, float momentum, "
         "float weight_decay, float eeta, float eps, Tensor? step=None, int t_offset=1, float grad_scale=1.0, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
-        "Tensor? gscale=None, Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False) -> Tensor");
+        "Tensor? gscale=None, Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False, "
+        "Tensor? guard=None) -> Tensor");
   m.impl("lars_flat", c10::DispatchKey::CUDA, &lars_flat);
   m.def("layer_norms(Tensor x, Tensor segs) -> Tensor");
   m.impl("layer_norms", c10::DispatchKey::CUDA, &layer_norms);

@@ -46,6 +46,13 @@ float* ema_shadow(const at::Tensor& e, const at::Tensor& p, double decay, const 
   TORCH_CHECK(decay > 0.0 && decay < 1.0, who, ": ema_decay must be in (0, 1), got ", decay);
   return (float*)e.data_ptr();
 }
+// The optional trailing guard of the flat optimizers: the non-finite guard's device ok, given as the
+// [3] result of grad_guard or as a one-element view of its ok. With ok == 0 the op stores nothing.
+const float* guard_ok(const at::Tensor& t, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && (t.numel() == 3 || t.numel() == 1), who,
+              ": guard is grad_guard's fp32 GPU [3] result or its ok element");
+  return (const float*)t.data_ptr() + (t.numel() == 3 ? 2 : 0);
+}
 // the clip factor of the EMA variants when the caller clips nothing: one fp32 1.0 per device, made once
 const float* unit_scale(const at::Tensor& like) {
   static at::Tensor one[64];
@@ -60,7 +67,7 @@ void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::opti
                double b1, double b2, double eps, at::Tensor step, double grad_scale, int64_t t_offset,
                std::string lr_kind, std::vector<double> lr_params, std::vector<int64_t> lr_boundaries,
                std::vector<double> lr_values, c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> ema,
-               double ema_decay, bool ema_num_updates) {
+               double ema_decay, bool ema_num_updates, c10::optional<at::Tensor> guard) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "adam_flat: fp32 GPU params");
   TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel() && g.numel() == p.numel(), "adam_flat: sizes");
   TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam_flat: int64 GPU step");
@@ -69,7 +76,14 @@ void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::opti
              pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
              flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
              (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
-  if (ema) {
+  if (guard) {  // the guarded instantiations (optim_guard.hip) of the clip and the EMA variants
+    const float* ok = guard_ok(*guard, "adam_flat");
+    const AdamClipArgs k{a, gscale ? clip_factor(*gscale, "adam_flat") : unit_scale(p)};
+    if (ema)
+      adam_apply_guard(AdamEmaGuardArgs{AdamEmaArgs{k, ema_shadow(*ema, p, ema_decay, "adam_flat"), (float)ema_decay,
+                                                    ema_num_updates ? 1 : 0}, ok}, cur());
+    else adam_apply_guard(AdamGuardArgs{k, ok}, cur());
+  } else if (ema) {
     const AdamClipArgs k{a, gscale ? clip_factor(*gscale, "adam_flat") : unit_scale(p)};
     adam_apply_ema(AdamEmaArgs{k, ema_shadow(*ema, p, ema_decay, "adam_flat"), (float)ema_decay, ema_num_updates ? 1 : 0},
                    cur());
@@ -84,7 +98,7 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
                    double lr, double momentum, double weight_decay, bool nesterov, double grad_scale,
                    c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind, std::vector<double> lr_params,
                    std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
-                   c10::optional<at::Tensor> gscale) {
+                   c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> guard) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "momentum_flat: fp32 GPU params");
   TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), "momentum_flat: int64 GPU step");
   const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
@@ -94,7 +108,10 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
             pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
             sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
             step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
-  if (gscale) sgd_apply_clip(SgdClipArgs{a, clip_factor(*gscale, "momentum_flat")}, cur());
+  if (guard)
+    sgd_apply_guard(SgdGuardArgs{SgdClipArgs{a, gscale ? clip_factor(*gscale, "momentum_flat") : unit_scale(p)},
+                                 guard_ok(*guard, "momentum_flat")}, cur());
+  else if (gscale) sgd_apply_clip(SgdClipArgs{a, clip_factor(*gscale, "momentum_flat")}, cur());
   else sgd_apply(a, cur());
 }
 
@@ -105,7 +122,8 @@ void momentum_ema_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g
                        double lr, double momentum, double weight_decay, bool nesterov, double grad_scale,
                        c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind,
                        std::vector<double> lr_params, std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
-                       c10::optional<at::Tensor> gscale, at::Tensor ema, double ema_decay, bool ema_num_updates) {
+                       c10::optional<at::Tensor> gscale, at::Tensor ema, double ema_decay, bool ema_num_updates,
+                       c10::optional<at::Tensor> guard) {
   const char* who = "momentum_ema_flat";
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
   TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), who, ": int64 GPU step");
@@ -120,7 +138,9 @@ void momentum_ema_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g
             sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
             step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
   const SgdClipArgs k{a, gscale ? clip_factor(*gscale, who) : unit_scale(p)};
-  sgd_apply_ema(SgdEmaArgs{k, ema_shadow(ema, p, ema_decay, who), (float)ema_decay, ema_num_updates ? 1 : 0}, cur());
+  const SgdEmaArgs e{k, ema_shadow(ema, p, ema_decay, who), (float)ema_decay, ema_num_updates ? 1 : 0};
+  if (guard) sgd_apply_guard(SgdEmaGuardArgs{e, guard_ok(*guard, who)}, cur());
+  else sgd_apply_ema(e, cur());
 }
 
 // The shadow update as a pass of its own, from parameters already updated: e' = e - (1 - d_t)(e - p),
@@ -145,6 +165,27 @@ at::Tensor grad_global_norm(const at::Tensor& g, double clip_norm, double grad_s
              (float*)part.data_ptr(), cur());
   grad_norm_finish((const float*)part.data_ptr(), grad_norm_blocks(g.numel()), (float)grad_scale, (float)clip_norm,
                    (float*)out.data_ptr(), cur());
+  return out;
+}
+
+// {norm, scale, ok} of the non-finite guard over a flat fp32 or bf16 buffer (grad_guard.hip): norm and
+// scale as grad_global_norm gives them (clip_norm = inf: no clipping, scale 1), ok = 1 if the norm is
+// finite, else ok = 0 and scale = 0. Not finite means an inf / NaN element or a norm that overflows
+// fp32. Adds 1 - ok to the int64 device counter `skipped`.
+at::Tensor grad_guard(const at::Tensor& g, double grad_scale, double clip_norm, at::Tensor skipped) {
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && (gb || g.scalar_type() == at::kFloat) && g.is_contiguous() && g.numel() >= 1,
+              "grad_guard: a contiguous fp32 or bf16 GPU tensor of at least one element");
+  TORCH_CHECK(skipped.is_cuda() && skipped.scalar_type() == at::kLong && skipped.numel() == 1 &&
+                  skipped.get_device() == g.get_device(),
+              "grad_guard: skipped is one int64 element on g's device");
+  TORCH_CHECK(clip_norm > 0.0, "grad_guard: clip_norm must be positive (inf: no clipping), got ", clip_norm);
+  auto out = at::empty({3}, g.options().dtype(at::kFloat));
+  auto part = at::empty({kGradNormMaxBlocks}, out.options());
+  grad_sumsq(gb ? nullptr : (const float*)g.data_ptr(), gb ? (const uint16_t*)g.data_ptr() : nullptr, g.numel(),
+             (float*)part.data_ptr(), cur());
+  grad_guard_finish((const float*)part.data_ptr(), grad_norm_blocks(g.numel()), (float)grad_scale, (float)clip_norm,
+                    (float*)out.data_ptr(), (int64_t*)skipped.data_ptr(), cur());
   return out;
 }
 
@@ -223,22 +264,25 @@ TORCH_LIBRARY(tfd, m) {
   m.def("adam_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, float lr, float b1, float b2, "
         "float eps, Tensor(e!) step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
         "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], Tensor? gscale=None, "
-        "Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False) -> ()");
+        "Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False, Tensor? guard=None) -> ()");
   m.impl("adam_flat", c10::DispatchKey::CUDA, &adam_flat);
   m.def("momentum_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
         "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
-        "Tensor? gscale=None) -> ()");
+        "Tensor? gscale=None, Tensor? guard=None) -> ()");
   m.impl("momentum_flat", c10::DispatchKey::CUDA, &momentum_flat);
   m.def("momentum_ema_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
         "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
-        "Tensor? gscale=None, *, Tensor(f!) ema, float ema_decay, bool ema_num_updates=False) -> ()");
+        "Tensor? gscale=None, *, Tensor(f!) ema, float ema_decay, bool ema_num_updates=False, "
+        "Tensor? guard=None) -> ()");
   m.impl("momentum_ema_flat", c10::DispatchKey::CUDA, &momentum_ema_flat);
   m.def("ema_flat(Tensor(a!) e, Tensor p, float decay, bool num_updates=False, Tensor? step=None, int t_offset=0) -> ()");
   m.impl("ema_flat", c10::DispatchKey::CUDA, &ema_flat);
   m.def("grad_global_norm(Tensor g, float clip_norm, float grad_scale=1.0) -> Tensor");
   m.impl("grad_global_norm", c10::DispatchKey::CUDA, &grad_global_norm);
+  m.def("grad_guard(Tensor g, float grad_scale, float clip_norm, Tensor(a!) skipped) -> Tensor");
+  m.impl("grad_guard", c10::DispatchKey::CUDA, &grad_guard);
   m.def("grad_accum_flat(Tensor(a!) acc, Tensor g, Tensor(b!)? out=None, bool first=False) -> ()");
   m.impl("grad_accum_flat", c10::DispatchKey::CUDA, &grad_accum_flat);
   m.def("grad_accum_tuned(Tensor(a!) acc, Tensor g, Tensor(b!)? out, bool first, int blocks, int loads) -> ()");

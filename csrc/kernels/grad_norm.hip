@@ -9,6 +9,7 @@
 //     {norm, scale}: norm = grad_scale * sqrt(sum), scale = clip_norm / max(norm, clip_norm) in fp32,
 //     exactly 1 while norm <= clip_norm. No special case for non-finite norms: inf gives scale 0; a NaN
 //     norm fails the compare, leaves scale at 1, and the NaN gradients propagate as without clipping.
+//     (The finish that does make a case of them, and skips the step, is grad_guard.hip's.)
 #include <math.h>
 
 #include "../common.h"

@@ -78,7 +78,11 @@ __device__ __forceinline__ void lw_store_partials(float s0, float s1, float* __r
   }
 }
 
-template <int MODE, bool BF>
+// GUARD (LAMB only, the one stage 1 that stores): the non-finite guard's ok is loaded with the other
+// scalars, and with ok == 0 neither m' nor v' is stored. The partials are stored either way -- every
+// entry by every launch -- so stage 2 runs on whatever they hold and its output is unspecified on a
+// skipped step.
+template <int MODE, bool BF, bool GUARD>
 __device__ __forceinline__ void lw_stage1_body(const LayerwiseArgs& a) {
   const LwBlock b = a.blocks[blockIdx.x];
   const int64_t v0 = b.first >> 2;
@@ -115,6 +119,8 @@ __device__ __forceinline__ void lw_stage1_body(const LayerwiseArgs& a) {
   }
   float mul = 1.f, ct = 0.f, lambda = 0.f;
   if (MODE != LW_NORMS) mul = a.grad_scale * *a.gscale;
+  bool store = true;  // wave-uniform
+  if (GUARD) store = *a.ok != 0.f;
   if (MODE == LW_LAMB) {
     const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
     ct = lamb_ct(a.beta1, a.beta2, t);
@@ -135,7 +141,7 @@ __device__ __forceinline__ void lw_stage1_body(const LayerwiseArgs& a) {
         v[j] = lamb_v(vv[u][j], g[j], c2);
         second[j] = lamb_u(pv[u][j], m[j], v[j], ct, a.eps, lambda);
       }
-      if (in[u]) {
+      if (store && in[u]) {
         const int64_t i = v0 + (int)threadIdx.x + u * kLwThreads;
         lw_st4(a.s1, i, m);
         lw_st4(a.s2, i, v);
@@ -151,8 +157,10 @@ __device__ __forceinline__ void lw_stage1_body(const LayerwiseArgs& a) {
     float second = g;
     if (MODE == LW_LAMB) {
       const float m = lamb_m(tm, g, c1), v = lamb_v(tv, g, c2);
-      a.s1[te] = m;
-      a.s2[te] = v;
+      if (store) {
+        a.s1[te] = m;
+        a.s2[te] = v;
+      }
       second = lamb_u(tp, m, v, ct, a.eps, lambda);
     }
     const float first = MODE == LW_NORMS ? g : tp;
@@ -163,8 +171,15 @@ __device__ __forceinline__ void lw_stage1_body(const LayerwiseArgs& a) {
 }
 template <int MODE>
 __global__ __launch_bounds__(kLwThreads) void lw_stage1_kernel(LayerwiseArgs a) {
-  if (a.gbf) lw_stage1_body<MODE, true>(a);
-  else lw_stage1_body<MODE, false>(a);
+  if constexpr (MODE == LW_LAMB) {
+    if (a.ok) {
+      if (a.gbf) lw_stage1_body<MODE, true, true>(a);
+      else lw_stage1_body<MODE, false, true>(a);
+      return;
+    }
+  }
+  if (a.gbf) lw_stage1_body<MODE, true, false>(a);
+  else lw_stage1_body<MODE, false, false>(a);
 }
 
 // one block per variable: its blocks' partials in fp64, in a fixed order (a lane takes every 256th
@@ -198,7 +213,10 @@ __global__ __launch_bounds__(kLwThreads) void lw_stage2_kernel(LayerwiseArgs a) 
   }
 }
 
-template <int MODE, bool BF, bool EMA>  // LW_LAMB or LW_LARS
+// GUARD: the non-finite guard's ok is loaded with the ratio and t, after the operands, and with
+// ok == 0 the block returns before its first store: p, accum, the bf16 shadow and the EMA shadow keep
+// their bits
+template <int MODE, bool BF, bool EMA, bool GUARD>  // LW_LAMB or LW_LARS
 __device__ __forceinline__ void lw_stage3_body(const LayerwiseArgs& a) {
   const LwBlock b = a.blocks[blockIdx.x];
   const int64_t v0 = b.first >> 2;
@@ -235,6 +253,9 @@ __device__ __forceinline__ void lw_stage3_body(const LayerwiseArgs& a) {
   // the ratio, t and the flags: loaded after the operands, awaited here
   const float r = a.out[3 * (int64_t)b.seg + 2];
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
+  if (GUARD) {
+    if (*a.ok == 0.f) return;  // wave-uniform
+  }
   const float lambda = (a.segs[b.seg].flags & LW_DECAY) ? a.weight_decay : 0.f;
   const float lr_r = lr_at(a.sched, t - 1) * r;
   const float omd = ema_omd_at(a.ema_decay, a.ema_num_updates, t);
@@ -277,18 +298,23 @@ __device__ __forceinline__ void lw_stage3_body(const LayerwiseArgs& a) {
   }
 }
 
-// the wire format and the EMA shadow are tested once, around the whole body
-template <int MODE>
-__global__ __launch_bounds__(kLwThreads) void lw_stage3_kernel(LayerwiseArgs a) {
+// the wire format, the EMA shadow and the guard are tested once, around the whole body
+template <int MODE, bool GUARD>
+__device__ __forceinline__ void lw_stage3_pick(const LayerwiseArgs& a) {
   if constexpr (MODE == LW_LARS) {  // LAMB's stage 3 does not read the gradient
     if (a.gbf) {
-      if (a.ema) lw_stage3_body<MODE, true, true>(a);
-      else lw_stage3_body<MODE, true, false>(a);
+      if (a.ema) lw_stage3_body<MODE, true, true, GUARD>(a);
+      else lw_stage3_body<MODE, true, false, GUARD>(a);
       return;
     }
   }
-  if (a.ema) lw_stage3_body<MODE, false, true>(a);
-  else lw_stage3_body<MODE, false, false>(a);
+  if (a.ema) lw_stage3_body<MODE, false, true, GUARD>(a);
+  else lw_stage3_body<MODE, false, false, GUARD>(a);
+}
+template <int MODE>
+__global__ __launch_bounds__(kLwThreads) void lw_stage3_kernel(LayerwiseArgs a) {
+  if (a.ok) lw_stage3_pick<MODE, true>(a);
+  else lw_stage3_pick<MODE, false>(a);
 }
 
 void lw_check(const LayerwiseArgs& a, const char* who, bool update) {

@@ -39,6 +39,9 @@ struct LayerwiseArgs {
   float* ema;           // moving average of the weights (ema.h), or null
   float ema_decay;
   int ema_num_updates;
+  const float* ok;      // non-finite guard (grad_guard.hip): device ok of {norm, scale, ok}, or null. With
+                        // *ok == 0 no stage stores to p, s1, s2, pbf or ema; partials and out are written
+                        // and hold nothing specified
 };
 
 void lamb_apply(const LayerwiseArgs& a, hipStream_t s);  // stages 1, 2, 3

@@ -106,6 +106,25 @@ template <class O>
 __device__ __forceinline__ const O& tail_args(const O& o) { return o; }
 __device__ __forceinline__ const MnistAdamArgs& tail_args(const MnistAdamEmaArgs& k) { return k.o; }
 
+// The non-finite guard (GuardArgs<K>, tfd_kernels.h; optim_guard.hip holds the instantiations): every
+// view above is that of the wrapped K. guard_load is ok of grad_guard.hip's {norm, scale, ok}, read from
+// the device once per thread through a uniform address -- a load like t and the clip factor -- and
+// guard_skip whether the kernel returns before its first store. For every other struct guard_load is an
+// empty tag and guard_skip a constant false, so those instantiations hold the code they held.
+struct NoGuard {};
+template <class K>
+__device__ __forceinline__ decltype(auto) optim_args(const GuardArgs<K>& g) { return optim_args(g.k); }
+template <class K>
+__device__ __forceinline__ float clip_load(const GuardArgs<K>& g) { return clip_load(g.k); }
+template <class K>
+__device__ __forceinline__ auto ema_of(const GuardArgs<K>& g) { return ema_of(g.k); }
+template <class K>
+__device__ __forceinline__ NoGuard guard_load(const K&) { return NoGuard{}; }
+template <class K>
+__device__ __forceinline__ float guard_load(const GuardArgs<K>& g) { return *g.ok; }
+__device__ __forceinline__ constexpr bool guard_skip(NoGuard) { return false; }
+__device__ __forceinline__ bool guard_skip(float ok) { return ok == 0.f; }
+
 __device__ __forceinline__ NoEma ema_omd(NoEma, int64_t) { return NoEma{}; }
 __device__ __forceinline__ float ema_omd(const EmaRef& r, int64_t t) { return ema_omd_at(r.decay, r.num_updates, t); }
 __device__ __forceinline__ NoEma ema_load4(NoEma, int64_t) { return NoEma{}; }

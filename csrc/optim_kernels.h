@@ -6,7 +6,9 @@
 // kernels with the gradient multiplier grad_scale * *gscale, the clip factor of global-norm clipping
 // read from the device (grad_norm.hip). A fourth, optim_ema.hip, takes them over AdamEmaArgs /
 // SgdEmaArgs: the clip variant plus the moving average of the weights, updated from p' while it is in
-// registers (ema.h). Separate code objects on purpose: see mnist_tail.h.
+// registers (ema.h). A fifth, optim_guard.hip, takes them over GuardArgs<...> of the clip and the EMA
+// wrappers: the same kernels, returning before their first store when the step's gradient is not finite
+// (grad_guard.hip). Separate code objects on purpose: see mnist_tail.h.
 #pragma once
 #include <math.h>
 
@@ -88,6 +90,8 @@ __global__ __launch_bounds__(kOptThreads) void adam_kernel(K k) {
   }
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
   const auto clip = clip_load(k);  // a load like t: issued here, awaited with it
+  const auto ok = guard_load(k);   // likewise (optim_const.h); nothing unless K is a guard wrapper
+  if (guard_skip(ok)) return;      // wave-uniform, before the first store: a skipped step writes nothing
   const auto omd = ema_omd(em, t);
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
@@ -140,6 +144,8 @@ __global__ __launch_bounds__(kOptThreads) void adam_ranges_kernel(K k, AdamRange
   }
   const int64_t t = (a.step ? *a.step : 0) + a.t_offset;
   const auto clip = clip_load(k);
+  const auto ok = guard_load(k);
+  if (guard_skip(ok)) return;
   const auto omd = ema_omd(em, t);
   const float b1p = powf(a.beta1, (float)t), b2p = powf(a.beta2, (float)t);
   const float lr_t = base_lr(a, t) * sqrtf(1.f - b2p) / (1.f - b1p);
@@ -172,12 +178,14 @@ __device__ __forceinline__ float sgd_ema_omd(const SgdArgs& a, const EmaRef& em)
 }
 // GradientDescent / Momentum (TF ApplyMomentum: accum = accum*mu + g; p -= lr*accum,
 // nesterov: p -= lr*(g + mu*accum)); optional decoupled-from-nothing L2 weight decay folded in g.
-template <class K>  // SgdConst, SgdArgs, SgdClipArgs or SgdEmaArgs
+template <class K>  // SgdConst, SgdArgs, SgdClipArgs, SgdEmaArgs or a guard wrapper of the last two
 __global__ __launch_bounds__(kOptThreads) void sgd_kernel(K k) {
   const auto& a = optim_args(k);
   const int64_t stride = (int64_t)gridDim.x * kOptThreads;
   const float lr = base_lr(a);
   const auto clip = clip_load(k);
+  const auto ok = guard_load(k);
+  if (guard_skip(ok)) return;
   const auto em = ema_of(k);
   const auto omd = sgd_ema_omd(a, em);
   for (int64_t i = (int64_t)blockIdx.x * kOptThreads + threadIdx.x; i < a.n; i += stride) {

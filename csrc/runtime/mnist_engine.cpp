@@ -12,6 +12,7 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <set>
 #include <string>
@@ -51,8 +52,12 @@ class MnistEngine : public torch::CustomClassHolder {
     gbf_ = at::zeros({TOTAL}, bf);
     step_ = at::zeros({1}, i64);
     tnext_ = at::zeros({1}, i64);
-    gnorm_ = at::zeros({2}, f32);  // {norm, scale} of the last clipped step (set_clip_norm)
+    // {norm, scale} of the last clipped step (set_clip_norm), then ok of the non-finite guard
+    // (set_skip_nonfinite) and its device counter of skipped steps
+    gnorm_ = at::zeros({3}, f32);
     gnorm_[1] = 1.0;
+    gnorm_[2] = 1.0;
+    skipped_ = at::zeros({1}, i64);
     gpart_ = at::zeros({kGradNormMaxBlocks}, f32);
     fc1_splits_ = mnist_fc1_splits((int)B_);
     wg2_splits_ = mnist_wg2_splits((int)B_);
@@ -255,7 +260,23 @@ class MnistEngine : public torch::CustomClassHolder {
   void set_clip_norm(double c) { clip_norm_ = c > 0 ? c : 0.0; }
   double clip_norm() const { return clip_norm_; }
   // {norm, scale} of the last clipped step, on the device ({0, 1} before the first)
-  at::Tensor grad_norm() { return gnorm_; }
+  at::Tensor grad_norm() { return gnorm_.narrow(0, 0, 2); }
+  // Non-finite guard, off by default. A step whose aggregated gradient is not finite is an identity
+  // update: the optimizer kernels return before their first store, so the parameters, the slots, the
+  // bf16 shadow and the EMA shadow keep their bits, and a device counter of skipped steps goes up by
+  // one. global_step and the micro-step counter advance as on any step -- the data cursor, the dropout
+  // key, the schedules, the EMA decay and Adam's t follow them: a skipped step consumes its batch and
+  // its t. "Not finite": the fp32 sum of squares of the aggregated gradient (grad_sumsq), finished in
+  // fp64 and scaled, is inf or NaN -- any inf / NaN element, and also finite gradients whose norm
+  // overflows fp32, which are skipped as well (grad_guard.hip). The step takes the whole-gradient path
+  // of set_clip_norm; with the guard on, grad_norm() reports {norm, scale} without clipping too. The
+  // counter is a statistic: no state depends on it and it is not checkpointed.
+  void set_skip_nonfinite(bool on) { guard_ = on; }
+  bool skip_nonfinite() const { return guard_; }
+  at::Tensor skipped_steps_tensor() { return skipped_; }
+  int64_t skipped_steps() { return skipped_.item<int64_t>(); }
+  // whether the last guarded step was applied (true before any)
+  bool last_step_ok() { return gnorm_[2].item<float>() != 0.f; }
   // tf.train.ExponentialMovingAverage of the weights (SyncReplicasOptimizer's variable_averages),
   // updated by the optimizer kernels themselves from p' in registers (csrc/ema.h): e' = e - (1 - d_t)
   // (e - p'), d_t = decay or, with num_updates, min(decay, (1 + t) / (10 + t)) from the device step
@@ -508,6 +529,10 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(lw_ && (zero_ || sfb_active())), lw_ == 1 ? "set_lamb" : "set_lars", " conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the per-variable norms need the whole aggregated gradient on every rank; use the all-reduce schedule");
+    // nor a whole-gradient sum of squares to call finite
+    TORCH_CHECK(!(guard_ && (zero_ || sfb_active())), "set_skip_nonfinite conflicts with ",
+                zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
+                ": the guard reads the whole aggregated gradient on every rank; use the all-reduce schedule");
     // each rank updates only its fc1 shard, so it would own only that shard of the averages
     TORCH_CHECK(!(ema_on() && zero_), "set_ema conflicts with ZeRO-1 (set_zero): each rank would hold only its fc1 "
                 "shard of the moving averages; use a schedule without ZeRO");
@@ -527,7 +552,7 @@ class MnistEngine : public torch::CustomClassHolder {
       train_step_accum(dp);
       return;
     }
-    if (clip_norm_ > 0 || lw_) {
+    if (clip_norm_ > 0 || lw_ || guard_) {
       train_step_clip(dp);
       return;
     }
@@ -794,7 +819,8 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_OPT, s);
   }
 
-  // Step with global-norm clipping (set_clip_norm) and / or a layer-wise optimizer (set_lamb, set_lars):
+  // Step with global-norm clipping (set_clip_norm), the non-finite guard (set_skip_nonfinite) and / or a
+  // layer-wise optimizer (set_lamb, set_lars):
   // one serial schedule for both dtypes, the shape of the unfused one-GPU step --
   //   s: forward -> backward a -> backward b -> conv-slab reduce (step bump) -> [DP: wait c]
   //      -> [clip: norm stage 1 -> norm stage 2] -> ONE optimizer over [0, TOTAL), t = global_step
@@ -876,11 +902,36 @@ class MnistEngine : public torch::CustomClassHolder {
   // The end of the steps that hold the whole aggregated gradient in one flat buffer (train_step_clip,
   // train_step_accum) -- grad_, or gbf_ with a bf16 wire (bf) -- after the step bump: [clip: norm stage
   // 1 -> norm stage 2] -> ONE optimizer over [0, TOTAL), t = global_step (layer-wise: its three stages).
+  // With the guard, stage 2 is the guard finish ({norm, scale, ok}, the skipped-step counter; scale
+  // exactly 1 without clipping) and the optimizer its guarded instantiation, which stores nothing when
+  // ok == 0. In DP the buffer is the all-reduced one, so every rank decides alike: whether a sum is
+  // finite does not depend on its order.
   void whole_gradient_tail(bool bf, double scale, hipStream_t s) {
     const int64_t* step = (const int64_t*)step_.data_ptr();
     float* pair = (float*)gnorm_.data_ptr();
     float* part = (float*)gpart_.data_ptr();
     const float* gscale = nullptr;  // the step's clip factor on the device; none without clipping
+    if (guard_) {
+      grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
+      grad_guard_finish(part, grad_norm_blocks(TOTAL), (float)scale,
+                        clip_norm_ > 0 ? (float)clip_norm_ : std::numeric_limits<float>::infinity(), pair,
+                        (int64_t*)skipped_.data_ptr(), s);
+      tag("grad_guard", s);
+      gscale = pair + 1;
+      const float* ok = pair + 2;
+      if (lw_) {
+        apply_layerwise(bf, scale, 0, step, gscale, s, ok);
+      } else if (ema_on()) {
+        if (opt_ == 0) adam_apply_guard(AdamEmaGuardArgs{ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
+        else sgd_apply_guard(SgdEmaGuardArgs{ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
+      } else {
+        if (opt_ == 0) adam_apply_guard(AdamGuardArgs{AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), gscale}, ok}, s);
+        else sgd_apply_guard(SgdGuardArgs{SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), gscale}, ok}, s);
+      }
+      tag("opt", s);
+      mark(P_OPT, s);
+      return;
+    }
     if (clip_norm_ > 0) {
       grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
       grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
@@ -1331,8 +1382,9 @@ class MnistEngine : public torch::CustomClassHolder {
     lw_ = kind;
   }
   // stages 1, 2, 3 over [0, TOTAL); gscale: the step's clip factor on the device, null without clipping
+  // ok: the non-finite guard's device ok, null without the guard
   void apply_layerwise(bool bf_grads, double grad_scale, int t_offset, const int64_t* t, const float* gscale,
-                       hipStream_t s) {
+                       hipStream_t s, const float* ok = nullptr) {
     LayerwiseArgs a{};
     a.p = (float*)params_.data_ptr();
     a.s1 = (float*)m_.data_ptr();
@@ -1357,6 +1409,7 @@ class MnistEngine : public torch::CustomClassHolder {
     a.t_offset = t_offset;
     a.grad_scale = (float)grad_scale;
     a.gscale = gscale ? gscale : (const float*)one_.data_ptr();
+    a.ok = ok;
     if (ema_on()) {
       ema_bf_stale_ = true;
       a.ema = (float*)ema_.data_ptr();
@@ -1638,6 +1691,9 @@ class MnistEngine : public torch::CustomClassHolder {
   // global-norm clipping (set_clip_norm): 0 = off; {norm, scale} and stage 1's per-block partials
   double clip_norm_ = 0.0;
   at::Tensor gnorm_, gpart_;
+  // non-finite guard (set_skip_nonfinite): ok is gnorm_[2]; the device counter of skipped steps
+  bool guard_ = false;
+  at::Tensor skipped_;
   // gradient accumulation (set_grad_accum): micro-batches per optimizer step (1 = off), the fp32
   // accumulator and the device micro-batch counter
   int64_t accum_ = 1;
@@ -1719,6 +1775,11 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("set_clip_norm", &MnistEngine::set_clip_norm)
       .def("clip_norm", &MnistEngine::clip_norm)
       .def("grad_norm", &MnistEngine::grad_norm)
+      .def("set_skip_nonfinite", &MnistEngine::set_skip_nonfinite)
+      .def("skip_nonfinite", &MnistEngine::skip_nonfinite)
+      .def("skipped_steps", &MnistEngine::skipped_steps)
+      .def("skipped_steps_tensor", &MnistEngine::skipped_steps_tensor)
+      .def("last_step_ok", &MnistEngine::last_step_ok)
       .def("set_ema", &MnistEngine::set_ema)
       .def("ema_decay", &MnistEngine::ema_decay)
       .def("ema_decay_at_step", &MnistEngine::ema_decay_at_step)

@@ -198,6 +198,28 @@ constexpr int kGradNormMaxBlocks = 512;
 int grad_norm_blocks(int64_t n);
 void grad_sumsq(const float* g, const uint16_t* gbf, int64_t n, float* partials, hipStream_t s);
 void grad_norm_finish(const float* partials, int nb, float grad_scale, float clip_norm, float* out, hipStream_t s);
+// Non-finite guard (grad_guard.hip): the finish of the same stage 1 that also decides whether the step
+// is applied. out = {norm, scale, ok}: norm and scale as grad_norm_finish writes them (clip_norm = +inf:
+// no clipping, scale exactly 1), ok = 1 if norm is finite, else ok = 0 and scale = 0. "Not finite" is
+// said of the fp32 sum of squares finished in fp64 and scaled: an inf or NaN element, and also finite
+// gradients whose norm overflows fp32 -- those steps are skipped as well. The same thread adds 1 - ok
+// to *skipped with a plain read-modify-write (one thread of one block: no atomics, nothing to zero), so
+// a replayed graph counts.
+void grad_guard_finish(const float* partials, int nb, float grad_scale, float clip_norm, float* out, int64_t* skipped,
+                       hipStream_t s);
+// The guarded optimizer instantiations (optim_guard.hip): wrappers over the clip and the EMA wrappers
+// with the device pointer to ok. A kernel that reads ok == 0 returns before its first store: p, the
+// slots, the bf16 shadow and the EMA shadow keep their bits.
+template <class K>
+struct GuardArgs { K k; const float* ok; };
+typedef GuardArgs<AdamClipArgs> AdamGuardArgs;
+typedef GuardArgs<SgdClipArgs> SgdGuardArgs;
+typedef GuardArgs<AdamEmaArgs> AdamEmaGuardArgs;
+typedef GuardArgs<SgdEmaArgs> SgdEmaGuardArgs;
+void adam_apply_guard(const AdamGuardArgs& a, hipStream_t s);
+void adam_apply_guard(const AdamEmaGuardArgs& a, hipStream_t s);
+void sgd_apply_guard(const SgdGuardArgs& a, hipStream_t s);
+void sgd_apply_guard(const SgdEmaGuardArgs& a, hipStream_t s);
 // roofline probes: the optimizer's byte floor (Adam's 28 B/param of traffic, optional extra fp32 read
 // stream of nx4 float4) and an empty launch (tools/debug/roofline_probe.py)
 void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf, const float* x, int64_t n4, int64_t nx4,

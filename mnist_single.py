@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -54,6 +54,9 @@ def main(argv=None):
                     "H2D) instead of the device-resident split with a per-epoch device shuffle")
     ap.add_argument("--clip_norm", type=float, default=0.0, help="tf.clip_by_global_norm on the gradient before "
                     "Adam (GPU: norm and clip factor taken on the device inside the step graph); 0 = off")
+    ap.add_argument("--skip_nonfinite", action="store_true", help="non-finite guard: a step whose gradient is not "
+                    "finite (an inf / NaN element, or a norm beyond fp32) is skipped -- parameters, optimizer slots and "
+                    "moving averages keep their bits (GPU: decided on the device inside the step graph)")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb", "lars"], help="adam (the reference), or a "
                     "layer-wise optimizer: every variable's update scaled by a trust ratio of two per-variable norms")
     ap.add_argument("--weight_decay", type=float, default=-1.0, help="--optimizer lamb / lars: weight decay "
@@ -84,7 +87,8 @@ def main(argv=None):
     ema = dict(ema_decay=a.ema_decay, ema_num_updates=bool(a.ema_num_updates)) if a.ema_decay > 0 else {}
     if a.optimizer == "adam" and a.weight_decay >= 0:
         ap.error("--weight_decay belongs to --optimizer lamb / lars")
-    common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, accum_steps=a.grad_accum_steps, **ema)
+    common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, accum_steps=a.grad_accum_steps,
+                  skip_nonfinite=bool(a.skip_nonfinite), **ema)
     if a.optimizer != "adam":
         common.update(skip_bias=bool(a.layerwise_skip_bias), **({} if a.weight_decay < 0 else dict(weight_decay=a.weight_decay)))
     if a.optimizer == "lamb":
@@ -131,6 +135,8 @@ def main(argv=None):
         if a.grad_accum_steps > 1:
             print("%d optimizer steps of %d micro-batches x %d images: %.1f images/sec" % (
                 step - 1, a.grad_accum_steps, a.batch_size, (step - 1) * step_rows / max(training_end_time - start_time, 1e-9)))
+        if a.skip_nonfinite and runner.skipped_steps() > 0:
+            print("--skip_nonfinite skipped %d of %d optimizer steps (gradient not finite)" % (runner.skipped_steps(), step - 1))
         if a.logdir:
             print("Saved %s" % saver.save(a.logdir, runner.state_dict_tf(), global_step=runner.global_step()))
     else:

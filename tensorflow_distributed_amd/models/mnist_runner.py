@@ -276,7 +276,15 @@ class TorchMnistRunner(MnistRunnerBase):
         a = self.applier
         if a.last_grad_norm is None:
             return float("nan"), 1.0
-        return float(a.last_grad_norm), float(a.last_clip_scale)
+        return float(a.last_grad_norm), float(a.last_clip_scale if a.last_clip_scale is not None else 1.0)
+
+    def skipped_steps(self) -> int:
+        """Steps the non-finite guard skipped so far (``skip_nonfinite`` on the config; a statistic, not
+        checkpointed)."""
+        return int(self.applier.skipped_steps)
+
+    def last_step_ok(self) -> bool:
+        return bool(self.applier.last_step_ok)
 
     def set_phase_timing(self, on: bool = True) -> None:
         pass
@@ -333,6 +341,10 @@ class NativeMnistRunner(MnistRunnerBase):
         if getattr(o, "clip_norm", None):
             # norm and clip factor taken on the device inside the step graph (csrc/kernels/grad_norm.hip)
             self.eng.set_clip_norm(float(o.clip_norm))
+        if getattr(o, "skip_nonfinite", False):
+            # decided on the device inside the step graph; the optimizer kernels store nothing on a skipped
+            # step (csrc/kernels/grad_guard.hip, optim_guard.hip)
+            self.eng.set_skip_nonfinite(True)
         self.comm = comm
         if comm is not None:
             self.eng.set_comm(comm, bf16_grads)
@@ -388,12 +400,23 @@ class NativeMnistRunner(MnistRunnerBase):
 
     def last_grad_norm(self) -> Tuple[float, float]:
         """``(norm, clip scale)`` of the last clipped step's averaged gradient: a host read of the
-        device pair, so call it only when something is logged. ``(nan, 1.0)`` without ``clip_norm``."""
-        if not self.eng.clip_norm() > 0:
+        device pair, so call it only when something is logged. ``(nan, 1.0)`` without ``clip_norm`` and
+        without ``skip_nonfinite``."""
+        if not (self.eng.clip_norm() > 0 or self.eng.skip_nonfinite()):
             return float("nan"), 1.0
         self.stream.synchronize()
         norm, scale = self.eng.grad_norm().tolist()
         return float(norm), float(scale)
+
+    def skipped_steps(self) -> int:
+        """Steps the non-finite guard skipped so far: a host read of the device counter (a statistic, not
+        checkpointed), so call it only when something is logged."""
+        self.stream.synchronize()
+        return int(self.eng.skipped_steps())
+
+    def last_step_ok(self) -> bool:
+        self.stream.synchronize()
+        return bool(self.eng.last_step_ok())
 
     def last_layer_norms(self):
         """A host read of the device table: call it only when something is logged."""

@@ -77,6 +77,11 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("clip_norm", 0.0, "tf.clip_by_global_norm on the aggregated (averaged) gradient before the "
                    "optimizer; on GPUs the norm and the clip factor are taken on the device inside the step "
                    "graph. 0 = off. Synchronous all-reduce training of --model mnist_cnn only")
+    f.DEFINE_boolean("skip_nonfinite", False, "Non-finite guard: an optimizer step whose aggregated gradient is not "
+                     "finite (an inf / NaN element, or a norm beyond fp32) is skipped -- parameters, optimizer slots "
+                     "and the moving averages keep their bits; global_step, the data cursor and the schedules advance. "
+                     "On GPUs decided on the device inside the step graph. Synchronous all-reduce training of --model "
+                     "mnist_cnn only")
     f.DEFINE_float("ema_decay", 0.0, "tf.train.ExponentialMovingAverage of the weights (SyncReplicasOptimizer's "
                    "variable_averages), updated inside the optimizer kernels after every aggregated update; "
                    "0 = off. The checkpoint carries <var>/ExponentialMovingAverage")
@@ -202,6 +207,8 @@ def _make_optimizer():
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
     acc = int(FLAGS.grad_accum_steps)
     ema = dict(ema_decay=FLAGS.ema_decay, ema_num_updates=bool(FLAGS.ema_num_updates)) if FLAGS.ema_decay > 0 else {}
+    if FLAGS.skip_nonfinite:  # rides with the EMA keywords: every config takes it
+        ema["skip_nonfinite"] = True
     if FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
         wd = {} if FLAGS.weight_decay < 0 else dict(weight_decay=FLAGS.weight_decay)
         common = dict(skip_bias=bool(FLAGS.layerwise_skip_bias), clip_norm=clip, **wd, **ema)
@@ -288,6 +295,28 @@ def check_clip_norm_flags(num_workers: int) -> None:
     if FLAGS.model != "mnist_cnn":
         raise ValueError("--clip_norm with --model %s: the ResNet runner's bucketed optimizer does not clip yet "
                          "(follow-up)" % FLAGS.model)
+
+
+def check_skip_nonfinite_flags(num_workers: int) -> None:
+    """--skip_nonfinite guards the aggregated update of synchronous all-reduce training. The combinations
+    it does not cover are flag errors, raised before any process group is built (every rank sees the same
+    flags), not silently unguarded runs."""
+    if not FLAGS.skip_nonfinite:
+        return
+    if not FLAGS.sync_replicas:
+        raise ValueError("--skip_nonfinite with --sync_replicas=False: the asynchronous parameter server applies each "
+                         "worker's gradient on its own, there is no aggregated gradient to guard")
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("--skip_nonfinite with backup workers (--replicas_to_aggregate=%d < %d workers): the "
+                         "accumulator paths have no guard" % (r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--skip_nonfinite with --model %s: the ResNet runner's bucketed optimizer has no guard"
+                         % FLAGS.model)
+    if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
+        raise ValueError("--skip_nonfinite with --dp_schedule=%s: the guard reads the whole aggregated gradient on "
+                         "every rank, which the SFB / ZeRO schedules never form; use the all-reduce schedule"
+                         % FLAGS.dp_schedule)
 
 
 def check_ema_flags(num_workers: int) -> None:
@@ -533,8 +562,9 @@ def dp_candidates(device_type: str, dtype: str):
         # --optimizer=lamb / lars: likewise for the per-variable norms (MnistEngine.set_lamb / set_lars)
         # --grad_accum_steps: the micro-batch gradients are summed whole before the one collective
         # (MnistEngine.set_grad_accum)
+        # --skip_nonfinite: the guard reads the whole aggregated gradient (MnistEngine.set_skip_nonfinite)
         if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS or \
-                FLAGS.grad_accum_steps > 1:
+                FLAGS.grad_accum_steps > 1 or FLAGS.skip_nonfinite:
             return ["allreduce"]
         # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
         return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
@@ -725,6 +755,7 @@ def main(argv=None) -> int:
     check_grad_accum_flags(len(FLAGS.worker_hosts.split(",")))
     check_layerwise_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
+    check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -788,7 +819,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     if sync:  # tf.train.SyncReplicasOptimizer's check of 1 <= replicas_to_aggregate <= total_num_replicas
         va = ExponentialMovingAverage(opt.ema_decay, opt.ema_num_updates) if opt.ema_decay else None
         SyncReplicasOptimizer(opt, replicas_to_aggregate=roles.r2a, total_num_replicas=num_workers,
-                              variable_averages=va).resolve(num_workers)
+                              variable_averages=va, skip_nonfinite=bool(opt.skip_nonfinite)).resolve(num_workers)
 
     dp_sched = dp_probe = dp_source = rccl = None
     if sync and num_workers > 1 and not roles.ps_mode:
@@ -877,6 +908,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 rec["grad_norm"], rec["clip_scale"] = runner.last_grad_norm()
             if FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
                 rec["trust_ratio"] = {k: v[2] for k, v in runner.last_layer_norms().items()}
+            if opt.skip_nonfinite:  # cumulative count, and whether this step's update was applied
+                rec["skipped_steps"], rec["step_ok"] = runner.skipped_steps(), runner.last_step_ok()
             if opt.ema_decay:  # d_t of this step's update (host mirror)
                 rec["ema_decay"] = ema_decay_at(opt.ema_decay, step, opt.ema_num_updates)
             if phase_timing:
@@ -929,7 +962,12 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         FLAGS.task_index, step_rows * (num_workers if sync else 1) * local_step / max(training_time, 1e-9), local_step,
         step_rows * (num_workers if sync else 1)))
     mean_accuracy = _validate(eval_batch)
-    metrics.log(event="final", global_step=step, training_time_s=training_time, mean_accuracy=mean_accuracy)
+    skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
+    if skipped > 0:
+        print("Worker %d: --skip_nonfinite skipped %d of %d optimizer steps (aggregated gradient not finite)"
+              % (FLAGS.task_index, skipped, local_step))
+    metrics.log(event="final", global_step=step, training_time_s=training_time, mean_accuracy=mean_accuracy,
+                **({"skipped_steps": skipped} if opt.skip_nonfinite else {}))
     if perf_rows:
         print(performance_table(perf_rows), end="")
     metrics.close()

@@ -44,6 +44,14 @@ from two L2 norms over that variable, and carry a weight decay. A variable has t
 ``r = 1``. :func:`trust_ratio`, :func:`lamb_update` and :func:`lars_update` are the fp64 definitions;
 the GPU forms the norms and the ratios on the device inside the step (``csrc/layerwise.h``,
 ``csrc/kernels/optim_layerwise.hip``). ``t`` is ``global_step`` after the update; no beta powers exist.
+
+Non-finite guard (the ``is_finite`` gate of TF's ``LossScaleOptimizer`` around ``apply_gradients``, the
+``if not np.isfinite(loss): skip`` idiom): ``skip_nonfinite`` on every optimizer config, off by default.
+A step whose aggregated gradient is not finite is an identity update -- parameters, slots and the EMA
+shadow keep their bits -- that still consumes its batch and its ``t``. :func:`nonfinite_guard` is the
+fp64 definition; the GPU engine decides on the device inside the step graph and counts the skipped steps
+there (``csrc/kernels/grad_guard.hip``, ``optim_guard.hip``). The count is a statistic: nothing depends
+on it and it is not checkpointed.
 """
 from __future__ import annotations
 
@@ -242,6 +250,7 @@ class AdamOptimizer:
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
     accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
@@ -257,6 +266,7 @@ class GradientDescentOptimizer:
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
     accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
@@ -274,6 +284,7 @@ class MomentumOptimizer:
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
     accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
 
     def __post_init__(self):
         _check_ema(self.ema_decay)
@@ -297,6 +308,7 @@ class LAMBOptimizer:
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
     accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
     name: str = "LAMB"
     kind: str = field(default="lamb", init=False)
 
@@ -322,6 +334,7 @@ class LARSOptimizer:
     ema_decay: Optional[float] = None
     ema_num_updates: bool = False
     accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
     name: str = "LARS"
     kind: str = field(default="lars", init=False)
 
@@ -394,20 +407,25 @@ class SyncReplicasOptimizer:
     # TF's variable_averages (variables_to_average: every trainable variable): forwarded to the base
     # optimizer's ema_decay / ema_num_updates, so the shadow is updated after every aggregated update
     variable_averages: Optional[ExponentialMovingAverage] = None
+    # the non-finite guard of the aggregated update: forwarded to the base optimizer's skip_nonfinite
+    # (None: whatever the base optimizer says)
+    skip_nonfinite: Optional[bool] = None
 
     def __post_init__(self):
+        import dataclasses
+
         va = self.variable_averages
         if va is not None:
-            import dataclasses
-
             self.opt = dataclasses.replace(self.opt, ema_decay=float(va.decay), ema_num_updates=bool(va.num_updates))
+        if self.skip_nonfinite is not None:
+            self.opt = dataclasses.replace(self.opt, skip_nonfinite=bool(self.skip_nonfinite))
 
     def resolve(self, num_workers: int) -> "SyncReplicasOptimizer":
         r = self.replicas_to_aggregate if self.replicas_to_aggregate is not None else num_workers
         t = self.total_num_replicas if self.total_num_replicas is not None else num_workers
         if not 1 <= r <= t:
             raise ValueError(f"replicas_to_aggregate={r} must be in [1, total_num_replicas={t}]")
-        return SyncReplicasOptimizer(self.opt, r, t, self.name, self.variable_averages)
+        return SyncReplicasOptimizer(self.opt, r, t, self.name, self.variable_averages, self.skip_nonfinite)
 
     @property
     def has_backup_workers(self) -> bool:
@@ -450,6 +468,25 @@ def clip_by_global_norm(g: torch.Tensor, clip_norm: float, scale: float = 1.0) -
         raise ValueError(f"clip_norm must be > 0, got {clip_norm!r}")
     norm = float(scale) * math.sqrt(float(g.detach().to(torch.float64).pow(2).sum().item()))
     return float(scale) * (c / (norm if norm > c else c)), norm
+
+
+FLT_MAX = 3.4028234663852886e38  # the largest finite fp32
+
+
+def nonfinite_guard(g: torch.Tensor, scale: float = 1.0) -> Tuple[float, bool]:
+    """``(norm, ok)`` of the non-finite guard over the flat gradient ``g``, in fp64.
+
+    ``norm = scale * sqrt(sum g_i^2)`` as :func:`clip_by_global_norm` takes it. ``ok`` is False when the
+    step is to be skipped: the sum of squares or the scaled norm is ``inf``, NaN or beyond the fp32 range.
+    That covers every ``inf`` / NaN element, and also finite gradients whose norm overflows fp32 -- the
+    device sums the squares in fp32 (``grad_sumsq``), so for it such a norm *is* ``inf``, and those
+    steps are skipped as well: a gradient whose norm fp32 cannot hold has no usable clip factor or
+    trust ratio either.
+    """
+    sumsq = float(g.detach().to(torch.float64).pow(2).sum().item())
+    norm = float(scale) * math.sqrt(sumsq) if sumsq >= 0.0 else float("nan")  # NaN fails the compare
+    ok = math.isfinite(sumsq) and sumsq <= FLT_MAX and math.isfinite(norm) and norm <= FLT_MAX
+    return norm, ok
 
 
 def check_segments(segments, numel: int):
@@ -508,10 +545,24 @@ class FlatApplier:
         # moving average of the weights (ema_decay on the config): starts as a copy of the parameters at
         # the first apply(), or where reset_ema() / load_ema() put it
         self.ema: Optional[torch.Tensor] = None
+        # non-finite guard (skip_nonfinite on the config): applies skipped so far (a statistic, not
+        # checkpointed) and whether the last apply() was applied
+        self.skipped_steps = 0
+        self.last_step_ok = True
 
     @torch.no_grad()
     def apply(self, p: torch.Tensor, g: torch.Tensor, scale: float = 1.0) -> None:
         o = self.opt
+        if getattr(o, "skip_nonfinite", False):
+            self.last_grad_norm, self.last_step_ok = nonfinite_guard(g, scale)
+            if not self.last_step_ok:
+                # an identity update that consumes its t: p, the slots and the shadow keep their bits
+                if getattr(o, "ema_decay", None) and self.ema is None:
+                    self.reset_ema(p)
+                self.last_clip_scale = 0.0
+                self.skipped_steps += 1
+                self.t += 1
+                return
         if getattr(o, "clip_norm", None):
             factor, self.last_grad_norm = clip_by_global_norm(g, o.clip_norm, scale)
             self.last_clip_scale = factor / scale

@@ -111,6 +111,9 @@ class Supervisor:
             vals.setdefault("global_norm", norm)
         for var, row in self._layer_norms().items():
             vals.setdefault("trust_ratio/" + var, row[2])
+        skipped = self._skipped_steps()
+        if skipped is not None:
+            vals.setdefault("skipped_steps", skipped)
         if now > t0:
             vals["global_step/sec"] = (global_step - s0) / (now - t0)
         self.writer.add_scalars(vals, global_step)
@@ -140,6 +143,14 @@ class Supervisor:
         read = getattr(self.runner, "last_grad_norm", None)
         norm = float(read()[0]) if read is not None else float("nan")
         return None if norm != norm else norm  # NaN: no clipped step yet
+
+    def _skipped_steps(self) -> Optional[int]:
+        """Steps the non-finite guard skipped so far when the runner's optimizer has ``skip_nonfinite`` (a
+        host read of the device counter on GPUs: only here, when a summary is written)."""
+        if not getattr(getattr(self.runner, "opt", None), "skip_nonfinite", False):
+            return None
+        read = getattr(self.runner, "skipped_steps", None)
+        return int(read()) if read is not None else None
 
     def save(self, global_step: Optional[int] = None) -> Optional[str]:
         if not (self.is_chief and self.logdir):
