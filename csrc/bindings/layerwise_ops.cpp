@@ -1,54 +1,12 @@
 // Torch ops of the layer-wise optimizers (csrc/layerwise.h, csrc/kernels/optim_layerwise.hip):
 // tfd::lamb_flat, tfd::lars_flat, tfd::layer_norms. A fragment of the `tfd` library, as conv_ops.cpp is.
-// Ops run on the caller's current HIP stream. (flat_schedule, clip_factor, ema_shadow and unit_scale repeat
-// ops.cpp's file-local helpers of the same names: a shared header is the follow-up.)
-#include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
+// Ops run on the caller's current HIP stream. The trailing arguments are read by flat_op_args.h.
 #include "../layerwise_kernels.h"
+#include "flat_op_args.h"
 
 namespace tfd {
 namespace {
-hipStream_t cur() { return c10::hip::getCurrentHIPStream().stream(); }
-
-// the trailing schedule arguments, as adam_flat takes them: no lr_params = constant at `lr`
-LrSchedule flat_schedule(double lr, const std::string& kind, const std::vector<double>& params,
-                         const std::vector<int64_t>& boundaries, const std::vector<double>& values) {
-  if (kind == "constant" && params.empty()) return lr_constant((float)lr);
-  TORCH_CHECK(params.empty() || (float)params[0] == (float)lr, "lr (", lr, ") and lr_params[0] (", params[0], ") disagree");
-  try {
-    return make_lr_schedule(kind, params.empty() ? std::vector<double>{lr} : params, boundaries, values);
-  } catch (const std::invalid_argument& e) {
-    TORCH_CHECK(false, e.what());
-  }
-}
-// gscale: the device clip factor, one fp32 element
-const float* clip_factor(const at::Tensor& t, const char* who) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == 1, who, ": gscale is one fp32 GPU element");
-  return (const float*)t.data_ptr();
-}
-// guard: the non-finite guard's device ok, the [3] result of grad_guard or a one-element view of its ok
-const float* guard_ok(const at::Tensor& t, const char* who) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && (t.numel() == 3 || t.numel() == 1), who,
-              ": guard is grad_guard's fp32 GPU [3] result or its ok element");
-  return (const float*)t.data_ptr() + (t.numel() == 3 ? 2 : 0);
-}
-float* ema_shadow(const at::Tensor& e, const at::Tensor& p, double decay, const char* who) {
-  TORCH_CHECK(e.is_cuda() && e.scalar_type() == at::kFloat && e.is_contiguous() && e.numel() == p.numel(), who,
-              ": ema is a contiguous fp32 GPU tensor of p's size");
-  TORCH_CHECK(decay > 0.0 && decay < 1.0, who, ": ema_decay must be in (0, 1), got ", decay);
-  return (float*)e.data_ptr();
-}
-// the clip factor when the caller clips nothing: one fp32 1.0 per device, made once (copied from the
-// host, so it is ready when the call returns)
-const float* unit_scale(const at::Tensor& like) {
-  static at::Tensor one[64];
-  const int d = like.get_device();
-  TORCH_CHECK(d >= 0 && d < 64, "device index");
-  if (!one[d].defined()) one[d] = at::ones({1}, at::kFloat).to(like.device());
-  return (const float*)one[d].data_ptr();
-}
+using namespace flat_op;  // cur, flat_schedule, clip_factor, guard_ok, ema_shadow, unit_scale
 
 // ---- layer-wise optimizers (csrc/layerwise.h, kernels/optim_layerwise.hip) ----
 // The block table of a segment table `segs` (int64 CPU [S,3] rows of begin, length, flags) over
@@ -121,13 +79,13 @@ LayerwiseArgs layerwise_args(const char* who, at::Tensor& p, at::Tensor& s1, con
   a.step = step ? (const int64_t*)step->data_ptr() : nullptr;
   a.t_offset = (int)t_offset;
   a.grad_scale = (float)grad_scale;
-  a.gscale = gscale ? clip_factor(*gscale, who) : unit_scale(p);
+  a.gscale = gscale ? clip_factor(*gscale, p, who) : unit_scale(p);
   if (ema) {
     a.ema = ema_shadow(*ema, p, ema_decay, who);
     a.ema_decay = (float)ema_decay;
     a.ema_num_updates = ema_num_updates ? 1 : 0;
   }
-  if (guard) a.ok = guard_ok(*guard, who);
+  if (guard) a.ok = guard_ok(*guard, p, who);
   return a;
 }
 

@@ -23,6 +23,7 @@
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
 #include "../mnist_layout.h"
+#include "../optim_rules.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
 #include "hip_util.h"
@@ -100,6 +101,11 @@ class MnistEngine : public torch::CustomClassHolder {
   at::Tensor grads_bf16() { return gbf_; }
   at::Tensor adam_m() { return m_; }
   at::Tensor adam_v() { return v_; }
+  // the third slot (centered RMSProp's mg): allocated at the first set_rmsprop(centered = true)
+  at::Tensor slot3() {
+    TORCH_CHECK(s3_.defined(), "slot3: set_rmsprop(centered = true) first");
+    return s3_;
+  }
   at::Tensor step_tensor() { return step_; }
   at::Tensor loss_rows() { return loss_row_; }
   at::Tensor correct_rows() { return correct_row_; }
@@ -207,6 +213,35 @@ class MnistEngine : public torch::CustomClassHolder {
     opt_ = momentum > 0 ? 2 : 1; momentum_ = momentum; nesterov_ = nesterov;
     lw_ = 0;
     sched_ = lr_constant((float)lr);
+  }
+  // RMSProp and Adagrad (csrc/optim_rules.h, kernels/optim_rules.hip): one launch over the range, on
+  // the unfused step -- the path Momentum takes. Slots: ms / accum in adam_v(), mom in adam_m(), the
+  // centered rule's mg in slot3(). The setters fill them with TF's initial values (ms = 1, mom = 0,
+  // mg = 0; accum = initial_accumulator_value) by ordinary tensor fills, outside any capture. They
+  // compose with set_lr_schedule, set_clip_norm, set_ema, set_skip_nonfinite, set_grad_accum and every DP
+  // schedule (ZeRO-1 shards the slots as it shards Adam's). Baked into graphs captured before the call.
+  void set_rmsprop(double lr, double decay, double momentum, double eps, bool centered) {
+    TORCH_CHECK(decay >= 0 && decay < 1 && momentum >= 0 && eps >= 0, "set_rmsprop: decay in [0, 1), momentum >= 0, eps >= 0");
+    opt_ = 3; rule_decay_ = decay; momentum_ = momentum; rule_eps_ = eps; centered_ = centered;
+    nesterov_ = false;
+    lw_ = 0;
+    sched_ = lr_constant((float)lr);
+    v_.fill_(1.0);
+    m_.zero_();
+    if (centered) {
+      if (!s3_.defined()) s3_ = at::zeros_like(m_);
+      else s3_.zero_();
+    }
+    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());  // the clip factor without clipping
+  }
+  void set_adagrad(double lr, double initial_accumulator_value) {
+    TORCH_CHECK(initial_accumulator_value > 0, "set_adagrad: initial_accumulator_value > 0");
+    opt_ = 4; centered_ = false;
+    nesterov_ = false;
+    lw_ = 0;
+    sched_ = lr_constant((float)lr);
+    v_.fill_(initial_accumulator_value);
+    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());
   }
   // Layer-wise optimizers (csrc/layerwise.h): every variable's update is scaled by a trust ratio formed
   // from two L2 norms over that variable, taken on the device inside the step (three launches over
@@ -400,7 +435,9 @@ class MnistEngine : public torch::CustomClassHolder {
     hipStream_t s = stream();
     ag_w(s);
     const int64_t r = rank_in_comm();
-    for (at::Tensor* t : {&params_, &m_, &v_}) {
+    std::vector<at::Tensor*> whole = {&params_, &m_, &v_};
+    if (opt_ == 3 && centered_) whole.push_back(&s3_);
+    for (at::Tensor* t : whole) {
       float* base = (float*)t->data_ptr() + OFF_WD1;
       if (comm_) comm_->all_gather_raw(base + r * zshard_, base, (size_t)zshard_, ncclFloat32, s);
       else ipc_->all_gather_raw(base, 4, zshard_, s);
@@ -495,6 +532,10 @@ class MnistEngine : public torch::CustomClassHolder {
       TORCH_CHECK(beg == 0 && end == TOTAL, "a layer-wise optimizer updates the whole flat buffer: a range has no "
                   "per-variable norm");
       apply_layerwise(bf_grads, grad_scale, t_offset, tsrc, nullptr, s);
+      return;
+    }
+    if (opt_ >= 3) {  // RMSProp / Adagrad: one struct carries the shadow, the clip factor and the guard
+      apply_rule(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc, nullptr, nullptr, s);
       return;
     }
     if (ema_on()) {  // the same launch, with the shadow's update (optim_ema.hip)
@@ -921,6 +962,8 @@ class MnistEngine : public torch::CustomClassHolder {
       const float* ok = pair + 2;
       if (lw_) {
         apply_layerwise(bf, scale, 0, step, gscale, s, ok);
+      } else if (opt_ >= 3) {
+        apply_rule(0, TOTAL, bf, scale, 0, step, gscale, ok, s);
       } else if (ema_on()) {
         if (opt_ == 0) adam_apply_guard(AdamEmaGuardArgs{ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
         else sgd_apply_guard(SgdEmaGuardArgs{ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
@@ -940,6 +983,8 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     if (lw_) {
       apply_layerwise(bf, scale, 0, step, gscale, s);
+    } else if (opt_ >= 3) {
+      apply_rule(0, TOTAL, bf, scale, 0, step, gscale, nullptr, s);
     } else if (ema_on()) {
       if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
       else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
@@ -1419,6 +1464,37 @@ class MnistEngine : public torch::CustomClassHolder {
     if (lw_ == 1) lamb_apply(a, s);
     else lars_apply(a, s);
   }
+  // RMSProp / Adagrad over [beg, beg + n); gscale: the step's clip factor on the device, null without
+  // clipping; ok: the non-finite guard's device ok, null without the guard
+  void apply_rule(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t,
+                  const float* gscale, const float* ok, hipStream_t s) {
+    RuleArgs a{};
+    a.p = (float*)params_.data_ptr() + beg;
+    a.s1 = (float*)v_.data_ptr() + beg;
+    a.s2 = opt_ == 3 ? (float*)m_.data_ptr() + beg : nullptr;
+    a.s3 = opt_ == 3 && centered_ ? (float*)s3_.data_ptr() + beg : nullptr;
+    a.g = bf_grads ? nullptr : (const float*)grad_.data_ptr() + beg;
+    a.gbf = bf_grads ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr;
+    a.pbf = (uint16_t*)pbf_.data_ptr() + beg;
+    a.n = n;
+    a.sched = sched_;
+    a.decay = (float)rule_decay_;
+    a.momentum = (float)momentum_;
+    a.eps = (float)rule_eps_;
+    a.step = t;
+    a.t_offset = t_offset;
+    a.grad_scale = (float)grad_scale;
+    a.gscale = gscale ? gscale : (const float*)one_.data_ptr();
+    a.ok = ok;
+    if (ema_on()) {
+      ema_bf_stale_ = true;
+      a.ema = (float*)ema_.data_ptr() + beg;
+      a.ema_decay = (float)ema_decay_;
+      a.ema_num_updates = ema_nu_ ? 1 : 0;
+    }
+    if (opt_ == 3) rmsprop_apply(a, centered_, s);
+    else adagrad_apply(a, s);
+  }
   // The EMA variants' arguments (set_ema): the clip wrapper -- gscale the step's clip factor, or a
   // device 1.0f without clipping -- and the shadow at the range's start. Each marks the bf16 image of
   // the shadow stale: an EMA launch is about to move the shadow.
@@ -1650,7 +1726,11 @@ class MnistEngine : public torch::CustomClassHolder {
   uint32_t seed_, rank_;
   int fc1_splits_, wg2_splits_;
   int64_t input_mode_ = 0;
-  int opt_ = 0;
+  int opt_ = 0;  // 0 Adam (LAMB), 1 GradientDescent, 2 Momentum (LARS), 3 RMSProp, 4 Adagrad
+  // RMSProp / Adagrad (set_rmsprop / set_adagrad): the rule's scalars and the centered rule's third slot
+  double rule_decay_ = 0.9, rule_eps_ = 1e-10;
+  bool centered_ = false;
+  at::Tensor s3_;
   // layer-wise optimizer (set_lamb / set_lars): 0 = off, 1 = LAMB, 2 = LARS; its tables and outputs
   int lw_ = 0, lw_nblocks_ = 0;
   double lw_wd_ = 0.0, lw_eeta_ = 0.0, lw_eps_ = 0.0;
@@ -1741,6 +1821,7 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("grads_bf16", &MnistEngine::grads_bf16)
       .def("adam_m", &MnistEngine::adam_m)
       .def("adam_v", &MnistEngine::adam_v)
+      .def("slot3", &MnistEngine::slot3)
       .def("step_tensor", &MnistEngine::step_tensor)
       .def("loss_rows", &MnistEngine::loss_rows)
       .def("correct_rows", &MnistEngine::correct_rows)
@@ -1767,6 +1848,8 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)
       .def("set_momentum", &MnistEngine::set_momentum)
+      .def("set_rmsprop", &MnistEngine::set_rmsprop)
+      .def("set_adagrad", &MnistEngine::set_adagrad)
       .def("set_lamb", &MnistEngine::set_lamb)
       .def("set_lars", &MnistEngine::set_lars)
       .def("layer_norms", &MnistEngine::layer_norms)

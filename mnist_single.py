@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -21,7 +21,8 @@ import torch  # noqa: E402
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
 from tensorflow_distributed_amd.training import checkpoint  # noqa: E402
-from tensorflow_distributed_amd.training.optimizers import AdamOptimizer, LAMBOptimizer, LARSOptimizer  # noqa: E402
+from tensorflow_distributed_amd.training.optimizers import (AdagradOptimizer, AdamOptimizer, LAMBOptimizer,  # noqa: E402
+                                                            LARSOptimizer, RMSPropOptimizer)
 from tensorflow_distributed_amd.utils import input_data  # noqa: E402
 
 # Parameters (mnist_single.py:17-21)
@@ -57,8 +58,16 @@ def main(argv=None):
     ap.add_argument("--skip_nonfinite", action="store_true", help="non-finite guard: a step whose gradient is not "
                     "finite (an inf / NaN element, or a norm beyond fp32) is skipped -- parameters, optimizer slots and "
                     "moving averages keep their bits (GPU: decided on the device inside the step graph)")
-    ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb", "lars"], help="adam (the reference), or a "
-                    "layer-wise optimizer: every variable's update scaled by a trust ratio of two per-variable norms")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb", "lars", "rmsprop", "adagrad"],
+                    help="adam (the reference); lamb / lars, layer-wise optimizers: every variable's update scaled by a "
+                    "trust ratio of two per-variable norms; rmsprop / adagrad (tf.train.RMSPropOptimizer / "
+                    "AdagradOptimizer)")
+    ap.add_argument("--rmsprop_decay", type=float, default=0.9, help="--optimizer rmsprop: decay of the averages")
+    ap.add_argument("--rmsprop_momentum", type=float, default=0.0, help="--optimizer rmsprop: momentum")
+    ap.add_argument("--rmsprop_epsilon", type=float, default=1e-10, help="--optimizer rmsprop: epsilon")
+    ap.add_argument("--rmsprop_centered", type=int, default=0, help="--optimizer rmsprop: 1 = the centered rule")
+    ap.add_argument("--adagrad_init_accum", type=float, default=0.1, help="--optimizer adagrad: "
+                    "initial_accumulator_value (> 0)")
     ap.add_argument("--weight_decay", type=float, default=-1.0, help="--optimizer lamb / lars: weight decay "
                     "(default: 0 for lamb, 1e-4 for lars)")
     ap.add_argument("--lars_eeta", type=float, default=1e-3, help="--optimizer lars: the trust coefficient")
@@ -85,16 +94,21 @@ def main(argv=None):
     mnist = input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed)
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and not a.cpu) else torch.device("cpu")
     ema = dict(ema_decay=a.ema_decay, ema_num_updates=bool(a.ema_num_updates)) if a.ema_decay > 0 else {}
-    if a.optimizer == "adam" and a.weight_decay >= 0:
+    if a.optimizer not in ("lamb", "lars") and a.weight_decay >= 0:
         ap.error("--weight_decay belongs to --optimizer lamb / lars")
     common = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None, accum_steps=a.grad_accum_steps,
                   skip_nonfinite=bool(a.skip_nonfinite), **ema)
-    if a.optimizer != "adam":
+    if a.optimizer in ("lamb", "lars"):
         common.update(skip_bias=bool(a.layerwise_skip_bias), **({} if a.weight_decay < 0 else dict(weight_decay=a.weight_decay)))
     if a.optimizer == "lamb":
         opt = LAMBOptimizer(a.learning_rate, **common)
     elif a.optimizer == "lars":
         opt = LARSOptimizer(a.learning_rate, eeta=a.lars_eeta, **common)
+    elif a.optimizer == "rmsprop":
+        opt = RMSPropOptimizer(a.learning_rate, a.rmsprop_decay, a.rmsprop_momentum, a.rmsprop_epsilon,
+                               bool(a.rmsprop_centered), **common)
+    elif a.optimizer == "adagrad":
+        opt = AdagradOptimizer(a.learning_rate, a.adagrad_init_accum, **common)
     else:
         opt = AdamOptimizer(a.learning_rate, **common)
     runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,

@@ -36,6 +36,12 @@ def _slot_suffixes(opt):
         return [("/" + opt.name, "m"), ("/" + opt.name + "_1", "v")]
     if kind == "lars":
         return [("/" + opt.name, "accum")]
+    if kind == "rmsprop":
+        # TF creates the slots in the order rms, mg (centered only), momentum
+        names = ["ms", "mg", "mom"] if opt.centered else ["ms", "mom"]
+        return [("/" + opt.name + ("_%d" % i if i else ""), n) for i, n in enumerate(names)]
+    if kind == "adagrad":
+        return [("/" + opt.name, "accum")]
     return [("/Adam", "m"), ("/Adam_1", "v"), ("/Momentum", "accum")]
 
 
@@ -186,9 +192,15 @@ class TorchMnistRunner(MnistRunnerBase):
     def load_flat(self, flat, slots, step):
         self.flat.copy_(flat.to(self.device))
         for name, t in slots.items():
-            key = {"accum": "m"}.get(name, name)
-            dst = getattr(self.applier, key, None)
-            if dst is not None:
+            # Momentum's / LARS's "accum" is FlatApplier's m; Adagrad's is its accum
+            dst = getattr(self.applier, name, None)
+            if dst is None:
+                dst = getattr(self.applier, {"accum": "m"}.get(name, name), None)
+            if dst is not None and (name in ("ms", "mom", "mg") or (name == "accum" and self.opt.kind == "adagrad")):
+                # the padding behind the variables is in no checkpoint: it keeps its initial value (a zero
+                # accumulator there would divide 0 by 0)
+                dst[:M.NUM_PARAMS].copy_(t.to(self.device)[:M.NUM_PARAMS])
+            elif dst is not None:
                 dst.copy_(t.to(self.device))
         self.applier.t = int(step)
         self._step = int(step)
@@ -333,6 +345,16 @@ class NativeMnistRunner(MnistRunnerBase):
             self.eng.set_lars(lr0, o.momentum, o.weight_decay, o.eeta, o.epsilon, bool(o.skip_bias))
         elif o.kind == "momentum":
             self.eng.set_momentum(lr0, o.momentum, o.use_nesterov)
+        elif o.kind == "rmsprop":
+            # one flat kernel per update (csrc/kernels/optim_rules.hip); the setter fills the slots with TF's
+            # initial values on the current stream, which the runner's own stream must not overtake
+            self.eng.set_rmsprop(lr0, o.decay, o.momentum, o.epsilon, bool(o.centered))
+            torch.cuda.current_stream(self.device).synchronize()
+        elif o.kind == "adagrad":
+            self.eng.set_adagrad(lr0, o.initial_accumulator_value)
+            torch.cuda.current_stream(self.device).synchronize()
+        elif o.kind != "sgd":
+            raise ValueError(f"NativeMnistRunner: no native rule for optimizer kind {o.kind!r}")
         else:
             self.eng.set_momentum(lr0, 0.0, False)
         if is_schedule(o.learning_rate):
@@ -495,6 +517,11 @@ class NativeMnistRunner(MnistRunnerBase):
                 self.eng.adam_m().copy_(slots.get("m", slots.get("accum")).to(self.device))
             if "v" in slots:
                 self.eng.adam_v().copy_(slots["v"].to(self.device))
+            for name, dst in self._rule_slots().items():  # RMSProp / Adagrad
+                if name in slots:
+                    # the padding behind the variables is in no checkpoint: it keeps its initial value (a
+                    # zero accumulator there would divide 0 by 0)
+                    dst[:M.NUM_PARAMS].copy_(slots[name].to(self.device)[:M.NUM_PARAMS])
             self.eng.step_tensor().fill_(int(step))
             self.eng.sync_micro_step()
             if self.ema_on:
@@ -517,8 +544,23 @@ class NativeMnistRunner(MnistRunnerBase):
             with torch.cuda.stream(self.stream):
                 self.eng.load_ema(self.eng.params())
 
+    def _rule_slots(self) -> "dict":
+        """RMSProp's / Adagrad's slots where the engine keeps them: ms / accum in the v buffer, mom in the m
+        buffer, the centered rule's mg in the third."""
+        o = self.opt
+        if o.kind == "rmsprop":
+            out = {"ms": self.eng.adam_v(), "mom": self.eng.adam_m()}
+            if o.centered:
+                out["mg"] = self.eng.slot3()
+            return out
+        if o.kind == "adagrad":
+            return {"accum": self.eng.adam_v()}
+        return {}
+
     def slot_tensors(self):
         self.stream.synchronize()
+        if self.opt.kind in ("rmsprop", "adagrad"):
+            return self._rule_slots()
         if self.opt.kind in ("adam", "lamb"):
             return {"m": self.eng.adam_m(), "v": self.eng.adam_v()}
         if self.opt.kind in ("momentum", "lars"):
@@ -547,6 +589,8 @@ class NativeMnistRunner(MnistRunnerBase):
             self.comm.broadcast(self.eng.params(), root)
             self.comm.broadcast(self.eng.adam_m(), root)
             self.comm.broadcast(self.eng.adam_v(), root)
+            if self.opt.kind == "rmsprop" and self.opt.centered:
+                self.comm.broadcast(self.eng.slot3(), root)
             self.comm.broadcast(self.eng.step_tensor(), root)
             self.eng.sync_micro_step()
             if self.ema_on:

@@ -112,8 +112,8 @@ class ParameterServerService:
                 for slot in self.applier.slots().values():  # hdr[3] = t; slots follow when hdr[1] < 0
                     if wk < 0 and n:
                         dist.recv(slot, src=src)
-                    elif wk >= 0:
-                        slot.zero_()
+                if wk >= 0:
+                    self.applier.reset_slots()  # a fresh start: TF's initial slot values
                 self.global_step = int(hdr[2])
                 self.applier.t = int(hdr[3])
                 self.initialized = True

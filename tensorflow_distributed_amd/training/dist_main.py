@@ -110,11 +110,18 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("save_summaries_secs", 120.0, "Summary (global_step/sec) period (chief)")
     f.DEFINE_integer("seed", 0, "Init seed (normal(0,1) params, chief)")
     f.DEFINE_float("keep_prob", 0.75, "Dropout keep probability during training")
-    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum", "lamb", "lars"], "Optimizer (reference: adam). lamb "
+    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum", "lamb", "lars", "rmsprop", "adagrad"],
+                  "Optimizer (reference: adam). lamb "
                   "and lars scale every variable's update by a trust ratio formed from two per-variable L2 norms "
                   "(on GPUs on the device, inside the step graph); synchronous all-reduce training of --model "
-                  "mnist_cnn only")
-    f.DEFINE_float("momentum", 0.9, "Momentum for --optimizer=momentum and lars")
+                  "mnist_cnn only. rmsprop and adagrad (tf.train.RMSPropOptimizer / AdagradOptimizer): --model "
+                  "mnist_cnn, every training mode but the GPU-resident parameter server")
+    f.DEFINE_float("momentum", 0.9, "Momentum for --optimizer=momentum and lars (rmsprop has --rmsprop_momentum)")
+    f.DEFINE_float("rmsprop_decay", 0.9, "--optimizer=rmsprop: decay of the moving averages of g^2 (and g, centered)")
+    f.DEFINE_float("rmsprop_momentum", 0.0, "--optimizer=rmsprop: momentum")
+    f.DEFINE_float("rmsprop_epsilon", 1e-10, "--optimizer=rmsprop: epsilon under the square root")
+    f.DEFINE_boolean("rmsprop_centered", False, "--optimizer=rmsprop: normalise by the estimated variance (a third slot)")
+    f.DEFINE_float("adagrad_init_accum", 0.1, "--optimizer=adagrad: initial_accumulator_value (> 0)")
     f.DEFINE_float("weight_decay", -1.0, "--optimizer=lamb / lars: weight decay lambda (default: 0 for lamb, 1e-4 for "
                    "lars)")
     f.DEFINE_float("lars_eeta", 1e-3, "--optimizer=lars: the trust coefficient eeta")
@@ -201,7 +208,8 @@ def _make_learning_rate():
 
 
 def _make_optimizer():
-    from .optimizers import AdamOptimizer, GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer, MomentumOptimizer
+    from .optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer,
+                             MomentumOptimizer, RMSPropOptimizer)
 
     lr = _make_learning_rate()
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
@@ -219,6 +227,11 @@ def _make_optimizer():
         return GradientDescentOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
     if FLAGS.optimizer == "momentum":
         return MomentumOptimizer(lr, FLAGS.momentum, clip_norm=clip, accum_steps=acc, **ema)
+    if FLAGS.optimizer == "rmsprop":  # --momentum is momentum's / lars's: RMSProp's own default is 0
+        return RMSPropOptimizer(lr, FLAGS.rmsprop_decay, FLAGS.rmsprop_momentum, FLAGS.rmsprop_epsilon,
+                                bool(FLAGS.rmsprop_centered), clip_norm=clip, accum_steps=acc, **ema)
+    if FLAGS.optimizer == "adagrad":
+        return AdagradOptimizer(lr, FLAGS.adagrad_init_accum, clip_norm=clip, accum_steps=acc, **ema)
     return AdamOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
 
 
@@ -249,6 +262,27 @@ def check_layerwise_flags(num_workers: int) -> None:
     if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
         raise ValueError("%s with --dp_schedule=%s: a sharded gradient has no per-variable norm; use the all-reduce "
                          "schedule" % (which, FLAGS.dp_schedule))
+
+
+RULE_OPTIMIZERS = ("rmsprop", "adagrad")
+
+
+def check_rules_flags(num_workers: int) -> None:
+    """--optimizer=rmsprop / adagrad run wherever the flat optimizer of --model mnist_cnn runs, and on the
+    host parameter server. The two places without the rules are flag errors, raised before any process
+    group is built; each is a follow-up."""
+    if FLAGS.optimizer not in RULE_OPTIMIZERS:
+        return
+    which = "--optimizer=%s" % FLAGS.optimizer
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the ResNet runner's bucketed optimizer has no such rule (follow-up)"
+                         % (which, FLAGS.model))
+    r2a = FLAGS.replicas_to_aggregate
+    ps_mode = not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts))
+    if ps_mode and FLAGS.ps_on_gpu and FLAGS.num_gpus > 0:
+        raise ValueError("%s with the GPU-resident parameter server: its shards know Adam, GradientDescent and "
+                         "Momentum only (follow-up); pass --ps_on_gpu=False for the host parameter server, which "
+                         "applies every rule" % which)
 
 
 def check_grad_accum_flags(num_workers: int) -> None:
@@ -754,6 +788,7 @@ def main(argv=None) -> int:
     check_clip_norm_flags(len(FLAGS.worker_hosts.split(",")))
     check_grad_accum_flags(len(FLAGS.worker_hosts.split(",")))
     check_layerwise_flags(len(FLAGS.worker_hosts.split(",")))
+    check_rules_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
 

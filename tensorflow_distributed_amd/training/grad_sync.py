@@ -80,7 +80,10 @@ class _PsSync:
         """Restored moments go back to the PS as host tensors (fresh init: None, the PS starts at zero)."""
         if not sv.restored_from:
             return None
-        return {("m" if k == "accum" else k): v.detach().float().cpu() for k, v in self.runner.slot_tensors().items()}
+        # the runners call Momentum's / LARS's slot "accum", FlatApplier keeps it in "m"; Adagrad's is "accum" in both
+        names = set(getattr(self.client, "slot_names", ()))
+        return {("m" if k == "accum" and "accum" not in names else k): v.detach().float().cpu()
+                for k, v in self.runner.slot_tensors().items()}
 
     def _straggle(self) -> None:
         if self.delay is not None:

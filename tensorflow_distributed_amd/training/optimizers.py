@@ -45,6 +45,13 @@ from two L2 norms over that variable, and carry a weight decay. A variable has t
 the GPU forms the norms and the ratios on the device inside the step (``csrc/layerwise.h``,
 ``csrc/kernels/optim_layerwise.hip``). ``t`` is ``global_step`` after the update; no beta powers exist.
 
+RMSProp and Adagrad (``tf.train.RMSPropOptimizer``, ``tf.train.AdagradOptimizer``): :class:`RMSPropOptimizer`
+(plain or centered, with or without momentum) and :class:`AdagradOptimizer`. :func:`rmsprop_update` and
+:func:`adagrad_update` are the fp64 definitions; slots start at TF's initial values (``ms = 1``,
+``mom = mg = 0``, ``accum = initial_accumulator_value``). The GPU applies them with one flat kernel each
+(``csrc/optim_rules.h``, ``csrc/kernels/optim_rules.hip``) inside the step, under the same schedules, clip,
+moving average, accumulation and guard as every other rule.
+
 Non-finite guard (the ``is_finite`` gate of TF's ``LossScaleOptimizer`` around ``apply_gradients``, the
 ``if not np.isfinite(loss): skip`` idiom): ``skip_nonfinite`` on every optimizer config, off by default.
 A step whose aggregated gradient is not finite is an identity update -- parameters, slots and the EMA
@@ -291,6 +298,79 @@ class MomentumOptimizer:
         _check_accum(self.accum_steps)
 
 
+@dataclass
+class RMSPropOptimizer:
+    """``ms' = ms + (g g - ms)(1 - decay)``; centered: ``mg' = mg + (g - mg)(1 - decay)``;
+    ``mom' = momentum mom + lr g / sqrt(ms' [- mg' mg'] + epsilon)``; ``p' = p - mom'`` (TF1 ApplyRMSProp /
+    ApplyCenteredRMSProp). Slots start as ``ms = 1``, ``mom = 0``, ``mg = 0``. The denominator is not
+    clamped: a centered ``ms' - mg'^2`` that rounding drives below ``-epsilon`` gives NaN, exactly as in TF."""
+    learning_rate: LearningRate = 0.001
+    decay: float = 0.9
+    momentum: float = 0.0
+    epsilon: float = 1e-10
+    centered: bool = False
+    name: str = "RMSProp"
+    kind: str = field(default="rmsprop", init=False)
+    clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
+        if not 0.0 <= self.decay < 1.0 or self.momentum < 0 or self.epsilon < 0:
+            raise ValueError("RMSProp: decay in [0, 1), momentum >= 0, epsilon >= 0")
+
+
+@dataclass
+class AdagradOptimizer:
+    """``accum' = accum + g g``; ``p' = p - lr g / sqrt(accum')`` (TF1 ApplyAdagrad). The slot starts at
+    ``initial_accumulator_value`` (> 0); there is no epsilon."""
+    learning_rate: LearningRate = 0.01
+    initial_accumulator_value: float = 0.1
+    name: str = "Adagrad"
+    kind: str = field(default="adagrad", init=False)
+    clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
+        if not self.initial_accumulator_value > 0:
+            raise ValueError(f"initial_accumulator_value must be > 0, got {self.initial_accumulator_value!r}")
+
+
+def rmsprop_update(p, ms, mom, g, lr: float, decay: float, momentum: float, epsilon: float, mg=None):
+    """One RMSProp update in fp64: ``(p', ms', mom')``, or ``(p', ms', mom', mg')`` when ``mg`` is given (the
+    centered rule). ``g`` is the gradient the optimizer consumes (scale and clip factor applied), ``lr`` the
+    rate of this update. No clamp on the denominator (see :class:`RMSPropOptimizer`)."""
+    f = lambda x: torch.as_tensor(x).detach().to(torch.float64)  # noqa: E731
+    p, ms, mom, g = f(p), f(ms), f(mom), f(g)
+    ms2 = ms + (g * g - ms) * (1.0 - decay)
+    if mg is None:
+        d = ms2 + epsilon
+    else:
+        mg2 = f(mg) + (g - f(mg)) * (1.0 - decay)
+        d = ms2 - mg2 * mg2 + epsilon
+    mom2 = momentum * mom + lr * g / d.sqrt()
+    if mg is None:
+        return p - mom2, ms2, mom2
+    return p - mom2, ms2, mom2, mg2
+
+
+def adagrad_update(p, accum, g, lr: float):
+    """One Adagrad update in fp64: ``(p', accum')``."""
+    f = lambda x: torch.as_tensor(x).detach().to(torch.float64)  # noqa: E731
+    p, accum, g = f(p), f(accum), f(g)
+    a2 = accum + g * g
+    return p - lr * g / a2.sqrt(), a2
+
+
 LW_DECAY, LW_ADAPT = 1, 2  # csrc/layerwise.h: LwFlags
 
 
@@ -532,6 +612,12 @@ class FlatApplier:
         z = lambda: torch.zeros(numel, dtype=torch.float32, device=device)  # noqa: E731
         self.m = z() if k in ("adam", "momentum", "lamb", "lars") else None
         self.v = z() if k in ("adam", "lamb") else None
+        # RMSProp: ms, mom and (centered) mg; Adagrad: accum -- at TF's initial values (reset_slots)
+        self.ms = z() if k == "rmsprop" else None
+        self.mom = z() if k == "rmsprop" else None
+        self.mg = z() if k == "rmsprop" and self.opt.centered else None
+        self.accum = z() if k == "adagrad" else None
+        self.reset_slots()
         # layer-wise optimizers: the variable table [(begin, length, flags)] (models.mnist_cnn.segments)
         # and, after every apply(), [(|p|, |u| or |g|, r)] per variable
         self.segments = None
@@ -580,6 +666,18 @@ class FlatApplier:
             p.sub_(lr_t * self.m / (self.v.sqrt() + o.epsilon))
         elif o.kind in LAYERWISE_KINDS:
             self._apply_layerwise(p, g, lr)
+        elif o.kind == "rmsprop":
+            # the fp64 definition; parameters and slots are stored in fp32
+            out = rmsprop_update(p, self.ms, self.mom, g, lr, o.decay, o.momentum, o.epsilon, self.mg)
+            p.copy_(out[0].to(torch.float32))
+            self.ms.copy_(out[1].to(torch.float32))
+            self.mom.copy_(out[2].to(torch.float32))
+            if self.mg is not None:
+                self.mg.copy_(out[3].to(torch.float32))
+        elif o.kind == "adagrad":
+            p2, a2 = adagrad_update(p, self.accum, g, lr)
+            p.copy_(p2.to(torch.float32))
+            self.accum.copy_(a2.to(torch.float32))
         elif o.kind == "momentum":
             self.m.mul_(o.momentum).add_(g)
             if o.use_nesterov:
@@ -622,12 +720,18 @@ class FlatApplier:
         if getattr(self.opt, "ema_decay", None):
             self.ema = e.detach().to(torch.float32).clone()
 
+    def reset_slots(self) -> None:
+        """Every slot at its initial value: 0, but TF's ``ms = 1`` for RMSProp and
+        ``initial_accumulator_value`` for Adagrad."""
+        for name, s in self.slots().items():
+            s.fill_(1.0 if name == "ms" else self.opt.initial_accumulator_value if name == "accum" else 0.0)
+
     def slots(self) -> "OrderedDict[str, torch.Tensor]":
+        """In a fixed order: ``m``, ``v``; RMSProp ``ms``, ``mg`` (centered), ``mom``; Adagrad ``accum``."""
         out = OrderedDict()
-        if self.m is not None:
-            out["m"] = self.m
-        if self.v is not None:
-            out["v"] = self.v
+        for name in ("m", "v", "ms", "mg", "mom", "accum"):
+            if getattr(self, name) is not None:
+                out[name] = getattr(self, name)
         return out
 
     def powers(self):
