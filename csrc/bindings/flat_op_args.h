@@ -1,7 +1,7 @@
-// What the flat optimizer ops share when they read their trailing arguments (layerwise_ops.cpp, rules_ops.cpp):
-// the schedule keywords, the device clip factor, the non-finite guard's ok, the EMA shadow and the device 1.0f
-// that stands in for the clip factor when the caller clips nothing. Host-only, header-only; every tensor is
-// checked to live on p's device.
+// What the flat optimizer ops share when they read their trailing arguments (ops.cpp, layerwise_ops.cpp,
+// rules_ops.cpp): the schedule keywords, the device clip factor, the non-finite guard's ok, the EMA shadow and the
+// device 1.0f that stands in for the clip factor when the caller clips nothing -- and flat_mods, which reads them
+// into the OptMods of optim_launch.h. Host-only, header-only; every tensor is checked to live on p's device.
 #pragma once
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../lr_schedule.h"
+#include "../optim_launch.h"
 
 namespace tfd {
 namespace flat_op {
@@ -61,6 +62,23 @@ inline const float* unit_scale(const at::Tensor& like) {
   TORCH_CHECK(d >= 0 && d < 64, "device index");
   if (!one[d].defined()) one[d] = at::ones({1}, at::kFloat).to(like.device());
   return (const float*)one[d].data_ptr();
+}
+// The trailing gscale / ema / guard of a flat op as the modifiers of its update. always_clip: the op's kernel
+// reads a clip factor in every variant (RuleArgs, LayerwiseArgs). The device 1.0f is made at the first call
+// that needs it, so an op that needs none allocates nothing (it may be inside a capture).
+inline OptMods flat_mods(const char* who, const at::Tensor& p, const c10::optional<at::Tensor>& gscale,
+                         const c10::optional<at::Tensor>& ema, double ema_decay, bool ema_num_updates,
+                         const c10::optional<at::Tensor>& guard, bool always_clip = false) {
+  OptMods m;
+  if (gscale) m.gscale = clip_factor(*gscale, p, who);
+  if (ema) {
+    m.ema = ema_shadow(*ema, p, ema_decay, who);
+    m.ema_decay = (float)ema_decay;
+    m.ema_num_updates = ema_num_updates ? 1 : 0;
+  }
+  if (guard) m.ok = guard_ok(*guard, p, who);
+  if (!m.gscale && (always_clip || opt_variant(m) != OptVariant::Plain)) m.one = unit_scale(p);
+  return m;
 }
 
 }  // namespace flat_op

@@ -6,7 +6,7 @@
 
 namespace tfd {
 namespace {
-using namespace flat_op;  // cur, flat_schedule, clip_factor, guard_ok, ema_shadow, unit_scale
+using namespace flat_op;  // cur, flat_schedule, flat_mods
 
 // ---- layer-wise optimizers (csrc/layerwise.h, kernels/optim_layerwise.hip) ----
 // The block table of a segment table `segs` (int64 CPU [S,3] rows of begin, length, flags) over
@@ -79,13 +79,7 @@ LayerwiseArgs layerwise_args(const char* who, at::Tensor& p, at::Tensor& s1, con
   a.step = step ? (const int64_t*)step->data_ptr() : nullptr;
   a.t_offset = (int)t_offset;
   a.grad_scale = (float)grad_scale;
-  a.gscale = gscale ? clip_factor(*gscale, p, who) : unit_scale(p);
-  if (ema) {
-    a.ema = ema_shadow(*ema, p, ema_decay, who);
-    a.ema_decay = (float)ema_decay;
-    a.ema_num_updates = ema_num_updates ? 1 : 0;
-  }
-  if (guard) a.ok = guard_ok(*guard, p, who);
+  apply_mods(a, flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard, true));
   return a;
 }
 

@@ -5,61 +5,17 @@
 #include <torch/library.h>
 
 #include "../grad_accum.h"
-#include "../tfd_kernels.h"
+#include "flat_op_args.h"  // with optim_launch.h
 
 namespace tfd {
 uint32_t crc32c_extend(uint32_t init, const void* data, size_t n);
 
 namespace {
-hipStream_t cur() { return c10::hip::getCurrentHIPStream().stream(); }
+using namespace flat_op;  // cur, flat_schedule, ema_shadow, flat_mods
 
 int64_t crc32c_op(const at::Tensor& bytes, int64_t init) {
   TORCH_CHECK(!bytes.is_cuda() && bytes.is_contiguous(), "crc32c: contiguous CPU tensor");
   return (int64_t)crc32c_extend((uint32_t)init, bytes.data_ptr(), (size_t)bytes.nbytes());
-}
-
-// the optional trailing schedule arguments of the flat ops: no lr_params = constant at `lr`
-LrSchedule flat_schedule(double lr, const std::string& kind, const std::vector<double>& params,
-                         const std::vector<int64_t>& boundaries, const std::vector<double>& values) {
-  if (kind == "constant" && params.empty()) return lr_constant((float)lr);
-  // lr_params[0] is the base rate: the positional lr must say the same, not be silently ignored
-  TORCH_CHECK(params.empty() || (float)params[0] == (float)lr, "lr (", lr, ") and lr_params[0] (", params[0], ") disagree");
-  try {
-    return make_lr_schedule(kind, params.empty() ? std::vector<double>{lr} : params, boundaries, values);
-  } catch (const std::invalid_argument& e) {
-    TORCH_CHECK(false, e.what());
-  }
-}
-
-// the optional trailing gscale of the flat optimizers: the device clip factor, one fp32 element (a
-// one-element view such as grad_global_norm(...)[1:2]) that multiplies grad_scale inside the kernel
-const float* clip_factor(const at::Tensor& t, const char* who) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == 1, who, ": gscale is one fp32 GPU element");
-  return (const float*)t.data_ptr();
-}
-
-// The optional trailing ema / ema_decay / ema_num_updates of the flat optimizers: the moving average
-// of the weights, updated by the same launch from p' (csrc/ema.h). Checks the shadow and the decay.
-float* ema_shadow(const at::Tensor& e, const at::Tensor& p, double decay, const char* who) {
-  TORCH_CHECK(e.is_cuda() && e.scalar_type() == at::kFloat && e.is_contiguous() && e.numel() == p.numel(), who,
-              ": ema is a contiguous fp32 GPU tensor of p's size");
-  TORCH_CHECK(decay > 0.0 && decay < 1.0, who, ": ema_decay must be in (0, 1), got ", decay);
-  return (float*)e.data_ptr();
-}
-// The optional trailing guard of the flat optimizers: the non-finite guard's device ok, given as the
-// [3] result of grad_guard or as a one-element view of its ok. With ok == 0 the op stores nothing.
-const float* guard_ok(const at::Tensor& t, const char* who) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && (t.numel() == 3 || t.numel() == 1), who,
-              ": guard is grad_guard's fp32 GPU [3] result or its ok element");
-  return (const float*)t.data_ptr() + (t.numel() == 3 ? 2 : 0);
-}
-// the clip factor of the EMA variants when the caller clips nothing: one fp32 1.0 per device, made once
-const float* unit_scale(const at::Tensor& like) {
-  static at::Tensor one[64];
-  const int d = like.get_device();
-  TORCH_CHECK(d >= 0 && d < 64, "device index");
-  if (!one[d].defined()) one[d] = at::ones({1}, like.options().dtype(at::kFloat));
-  return (const float*)one[d].data_ptr();
 }
 
 // Adam's t = *step + t_offset; the schedule is evaluated on the device at s = t - 1
@@ -76,22 +32,24 @@ void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::opti
              pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
              flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
              (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
-  if (guard) {  // the guarded instantiations (optim_guard.hip) of the clip and the EMA variants
-    const float* ok = guard_ok(*guard, "adam_flat");
-    const AdamClipArgs k{a, gscale ? clip_factor(*gscale, "adam_flat") : unit_scale(p)};
-    if (ema)
-      adam_apply_guard(AdamEmaGuardArgs{AdamEmaArgs{k, ema_shadow(*ema, p, ema_decay, "adam_flat"), (float)ema_decay,
-                                                    ema_num_updates ? 1 : 0}, ok}, cur());
-    else adam_apply_guard(AdamGuardArgs{k, ok}, cur());
-  } else if (ema) {
-    const AdamClipArgs k{a, gscale ? clip_factor(*gscale, "adam_flat") : unit_scale(p)};
-    adam_apply_ema(AdamEmaArgs{k, ema_shadow(*ema, p, ema_decay, "adam_flat"), (float)ema_decay, ema_num_updates ? 1 : 0},
-                   cur());
-  } else if (gscale) {
-    adam_apply_clip(AdamClipArgs{a, clip_factor(*gscale, "adam_flat")}, cur());
-  } else {
-    adam_apply(a, cur());
-  }
+  adam_launch(a, flat_mods("adam_flat", p, gscale, ema, ema_decay, ema_num_updates, guard), cur());
+}
+
+// what momentum_flat and momentum_ema_flat share: the checks both make and the kernel's arguments
+SgdArgs sgd_flat_args(const char* who, at::Tensor& p, const c10::optional<at::Tensor>& mom, const at::Tensor& g,
+                      const c10::optional<at::Tensor>& pbf, double lr, double momentum, double weight_decay, bool nesterov,
+                      double grad_scale, const c10::optional<at::Tensor>& step, int64_t t_offset, const std::string& lr_kind,
+                      const std::vector<double>& lr_params, const std::vector<int64_t>& lr_boundaries,
+                      const std::vector<double>& lr_values) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
+  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), who, ": int64 GPU step");
+  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
+  TORCH_CHECK(sc.kind == LR_CONSTANT || step, who, ": a schedule needs the device step tensor");
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  return SgdArgs{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
+                 pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
+                 sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
+                 step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
 }
 
 void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
@@ -99,20 +57,10 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
                    c10::optional<at::Tensor> step, int64_t t_offset, std::string lr_kind, std::vector<double> lr_params,
                    std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
                    c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> guard) {
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "momentum_flat: fp32 GPU params");
-  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), "momentum_flat: int64 GPU step");
-  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
-  TORCH_CHECK(sc.kind == LR_CONSTANT || step, "momentum_flat: a schedule needs the device step tensor");
-  const bool gb = g.scalar_type() == at::kBFloat16;
-  SgdArgs a{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
-            pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-            sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
-            step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
-  if (guard)
-    sgd_apply_guard(SgdGuardArgs{SgdClipArgs{a, gscale ? clip_factor(*gscale, "momentum_flat") : unit_scale(p)},
-                                 guard_ok(*guard, "momentum_flat")}, cur());
-  else if (gscale) sgd_apply_clip(SgdClipArgs{a, clip_factor(*gscale, "momentum_flat")}, cur());
-  else sgd_apply(a, cur());
+  const char* who = "momentum_flat";
+  const SgdArgs a = sgd_flat_args(who, p, mom, g, pbf, lr, momentum, weight_decay, nesterov, grad_scale, step, t_offset,
+                                  lr_kind, lr_params, lr_boundaries, lr_values);
+  sgd_launch(a, flat_mods(who, p, gscale, c10::nullopt, 0.0, false, guard), cur());
 }
 
 // momentum_flat with the moving average of the weights updated by the same launch (csrc/ema.h): the
@@ -125,22 +73,12 @@ void momentum_ema_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g
                        c10::optional<at::Tensor> gscale, at::Tensor ema, double ema_decay, bool ema_num_updates,
                        c10::optional<at::Tensor> guard) {
   const char* who = "momentum_ema_flat";
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
-  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), who, ": int64 GPU step");
-  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
-  TORCH_CHECK(sc.kind == LR_CONSTANT || step, who, ": a schedule needs the device step tensor");
+  const SgdArgs a = sgd_flat_args(who, p, mom, g, pbf, lr, momentum, weight_decay, nesterov, grad_scale, step, t_offset,
+                                  lr_kind, lr_params, lr_boundaries, lr_values);
   TORCH_CHECK(!ema_num_updates || step, who, ": ema_num_updates needs the device step tensor");
   TORCH_CHECK(g.numel() == p.numel() && (!mom || mom->numel() == p.numel()) && (!pbf || pbf->numel() == p.numel()), who,
               ": sizes");
-  const bool gb = g.scalar_type() == at::kBFloat16;
-  SgdArgs a{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
-            pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-            sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
-            step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
-  const SgdClipArgs k{a, gscale ? clip_factor(*gscale, who) : unit_scale(p)};
-  const SgdEmaArgs e{k, ema_shadow(ema, p, ema_decay, who), (float)ema_decay, ema_num_updates ? 1 : 0};
-  if (guard) sgd_apply_guard(SgdEmaGuardArgs{e, guard_ok(*guard, who)}, cur());
-  else sgd_apply_ema(e, cur());
+  sgd_launch(a, flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard), cur());
 }
 
 // The shadow update as a pass of its own, from parameters already updated: e' = e - (1 - d_t)(e - p),

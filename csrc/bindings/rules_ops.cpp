@@ -6,7 +6,7 @@
 
 namespace tfd {
 namespace {
-using namespace flat_op;  // cur, flat_schedule, clip_factor, guard_ok, ema_shadow, step_ptr, unit_scale
+using namespace flat_op;  // cur, flat_schedule, step_ptr, flat_mods
 
 float* slot_ptr(const at::Tensor& s, const at::Tensor& p, const char* who, const char* name) {
   TORCH_CHECK(s.is_cuda() && s.get_device() == p.get_device() && s.scalar_type() == at::kFloat && s.is_contiguous() &&
@@ -43,13 +43,7 @@ RuleArgs rule_args(const char* who, at::Tensor& p, const at::Tensor& g, const c1
   a.step = step_p;
   a.t_offset = (int)t_offset;
   a.grad_scale = (float)grad_scale;
-  a.gscale = gscale ? clip_factor(*gscale, p, who) : unit_scale(p);
-  if (ema) {
-    a.ema = ema_shadow(*ema, p, ema_decay, who);
-    a.ema_decay = (float)ema_decay;
-    a.ema_num_updates = ema_num_updates ? 1 : 0;
-  }
-  if (guard) a.ok = guard_ok(*guard, p, who);
+  apply_mods(a, flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard, true));
   return a;
 }
 // the launchers' own checks (alignment) as torch errors

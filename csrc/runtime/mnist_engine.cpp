@@ -23,6 +23,7 @@
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
 #include "../mnist_layout.h"
+#include "../optim_launch.h"
 #include "../optim_rules.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
@@ -33,6 +34,9 @@ namespace tfd {
 using namespace mnist;
 
 class MnistEngine : public torch::CustomClassHolder {
+  // the update rule (not part of the torch class); LAMB runs on Adam's settings and slots, LARS on Momentum's
+  enum class OptKind { Adam, Sgd, Momentum, RmsProp, Adagrad };
+  enum class LwKind { None, Lamb, Lars };
  public:
   MnistEngine(int64_t batch, int64_t device, double keep_prob, int64_t seed, int64_t rank)
       : B_(batch), device_(device), keep_prob_(keep_prob), seed_((uint32_t)seed), rank_((uint32_t)rank) {
@@ -59,6 +63,8 @@ class MnistEngine : public torch::CustomClassHolder {
     gnorm_[1] = 1.0;
     gnorm_[2] = 1.0;
     skipped_ = at::zeros({1}, i64);
+    // OptMods::one (optim_launch.h); copied from the host: ready whichever stream the first step runs on
+    one_ = at::ones({1}, at::kFloat).to(params_.device());
     gpart_ = at::zeros({kGradNormMaxBlocks}, f32);
     fc1_splits_ = mnist_fc1_splits((int)B_);
     wg2_splits_ = mnist_wg2_splits((int)B_);
@@ -205,14 +211,12 @@ class MnistEngine : public torch::CustomClassHolder {
   }
 
   void set_adam(double lr, double b1, double b2, double eps) {
-    opt_ = 0; b1_ = b1; b2_ = b2; eps_ = eps;
-    lw_ = 0;
-    sched_ = lr_constant((float)lr);
+    b1_ = b1; b2_ = b2; eps_ = eps;
+    set_optimizer(OptKind::Adam, lr);
   }
   void set_momentum(double lr, double momentum, bool nesterov) {
-    opt_ = momentum > 0 ? 2 : 1; momentum_ = momentum; nesterov_ = nesterov;
-    lw_ = 0;
-    sched_ = lr_constant((float)lr);
+    momentum_ = momentum; nesterov_ = nesterov;
+    set_optimizer(momentum > 0 ? OptKind::Momentum : OptKind::Sgd, lr);
   }
   // RMSProp and Adagrad (csrc/optim_rules.h, kernels/optim_rules.hip): one launch over the range, on
   // the unfused step -- the path Momentum takes. Slots: ms / accum in adam_v(), mom in adam_m(), the
@@ -222,26 +226,22 @@ class MnistEngine : public torch::CustomClassHolder {
   // schedule (ZeRO-1 shards the slots as it shards Adam's). Baked into graphs captured before the call.
   void set_rmsprop(double lr, double decay, double momentum, double eps, bool centered) {
     TORCH_CHECK(decay >= 0 && decay < 1 && momentum >= 0 && eps >= 0, "set_rmsprop: decay in [0, 1), momentum >= 0, eps >= 0");
-    opt_ = 3; rule_decay_ = decay; momentum_ = momentum; rule_eps_ = eps; centered_ = centered;
+    rule_decay_ = decay; momentum_ = momentum; rule_eps_ = eps; centered_ = centered;
     nesterov_ = false;
-    lw_ = 0;
-    sched_ = lr_constant((float)lr);
+    set_optimizer(OptKind::RmsProp, lr);
     v_.fill_(1.0);
     m_.zero_();
     if (centered) {
       if (!s3_.defined()) s3_ = at::zeros_like(m_);
       else s3_.zero_();
     }
-    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());  // the clip factor without clipping
   }
   void set_adagrad(double lr, double initial_accumulator_value) {
     TORCH_CHECK(initial_accumulator_value > 0, "set_adagrad: initial_accumulator_value > 0");
-    opt_ = 4; centered_ = false;
+    centered_ = false;
     nesterov_ = false;
-    lw_ = 0;
-    sched_ = lr_constant((float)lr);
+    set_optimizer(OptKind::Adagrad, lr);
     v_.fill_(initial_accumulator_value);
-    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());
   }
   // Layer-wise optimizers (csrc/layerwise.h): every variable's update is scaled by a trust ratio formed
   // from two L2 norms over that variable, taken on the device inside the step (three launches over
@@ -252,17 +252,17 @@ class MnistEngine : public torch::CustomClassHolder {
   // set_momentum switch back. Baked into graphs captured before the call: capture again.
   void set_lamb(double lr, double b1, double b2, double eps, double weight_decay, bool skip_bias) {
     TORCH_CHECK(weight_decay >= 0, "set_lamb: weight_decay >= 0");
-    opt_ = 0; b1_ = b1; b2_ = b2; eps_ = eps;
+    b1_ = b1; b2_ = b2; eps_ = eps;
     lw_wd_ = weight_decay;
-    sched_ = lr_constant((float)lr);
-    set_layerwise(1, skip_bias);
+    set_optimizer(OptKind::Adam, lr);
+    set_layerwise(LwKind::Lamb, skip_bias);
   }
   void set_lars(double lr, double momentum, double weight_decay, double eeta, double eps, bool skip_bias) {
     TORCH_CHECK(weight_decay >= 0 && eeta > 0 && eps >= 0, "set_lars: weight_decay >= 0, eeta > 0, eps >= 0");
-    opt_ = 2; momentum_ = momentum; nesterov_ = false;
+    momentum_ = momentum; nesterov_ = false;
     lw_wd_ = weight_decay; lw_eeta_ = eeta; lw_eps_ = eps;
-    sched_ = lr_constant((float)lr);
-    set_layerwise(2, skip_bias);
+    set_optimizer(OptKind::Momentum, lr);
+    set_layerwise(LwKind::Lars, skip_bias);
   }
   // [8,3] = {|p|, |u| (LAMB) or |g| (LARS), r} of the last layer-wise step, on the device, in the flat
   // layout's order: wc1, bc1, wc2, bc2, wd1, bd1, out, out_b
@@ -326,10 +326,7 @@ class MnistEngine : public torch::CustomClassHolder {
       ema_decay_ = 0.0;
       return;
     }
-    if (!ema_.defined()) {
-      ema_ = at::empty_like(params_);
-      one_ = at::ones({1}, params_.options());  // the clip factor of the EMA variants without clipping
-    }
+    if (!ema_.defined()) ema_ = at::empty_like(params_);
     if (!ema_on()) {
       ema_.copy_(params_);
       ema_bf_stale_ = true;
@@ -436,7 +433,7 @@ class MnistEngine : public torch::CustomClassHolder {
     ag_w(s);
     const int64_t r = rank_in_comm();
     std::vector<at::Tensor*> whole = {&params_, &m_, &v_};
-    if (opt_ == 3 && centered_) whole.push_back(&s3_);
+    if (opt_ == OptKind::RmsProp && centered_) whole.push_back(&s3_);
     for (at::Tensor* t : whole) {
       float* base = (float*)t->data_ptr() + OFF_WD1;
       if (comm_) comm_->all_gather_raw(base + r * zshard_, base, (size_t)zshard_, ncclFloat32, s);
@@ -523,33 +520,29 @@ class MnistEngine : public torch::CustomClassHolder {
   void apply_optimizer(double grad_scale) {
     apply_optimizer_range(0, TOTAL, grad_scale, 0, stream());
   }
-  // Optimizer over the flat range [beg, end) on stream s; t = global_step + t_offset.
+  // Optimizer over the flat range [beg, end) on stream s; t = global_step + t_offset. The one place that
+  // chooses between the layer-wise optimizers, the rules, Adam and SGD; optim_launch.h picks the variant from
+  // mods(). gscale: the step's clip factor on the device, ok: the non-finite guard's device ok; null without.
   void apply_optimizer_range(int64_t beg, int64_t end, double grad_scale, int t_offset, hipStream_t s,
-                             const int64_t* tsrc = nullptr) {
+                             const int64_t* tsrc = nullptr, const float* gscale = nullptr, const float* ok = nullptr) {
     if (!tsrc) tsrc = (const int64_t*)step_.data_ptr();
     const bool bf_grads = bf16_comm_ && dp();
-    if (lw_) {
+    const OptMods m = mods(beg, gscale, ok);
+    if (layerwise()) {
       TORCH_CHECK(beg == 0 && end == TOTAL, "a layer-wise optimizer updates the whole flat buffer: a range has no "
                   "per-variable norm");
-      apply_layerwise(bf_grads, grad_scale, t_offset, tsrc, nullptr, s);
-      return;
+      apply_layerwise(bf_grads, grad_scale, t_offset, tsrc, m, s);
+    } else if (is_rule()) {
+      apply_rule(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc, m, s);
+    } else if (opt_ == OptKind::Adam) {
+      adam_launch(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), m, s);
+    } else {
+      sgd_launch(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), m, s);
     }
-    if (opt_ >= 3) {  // RMSProp / Adagrad: one struct carries the shadow, the clip factor and the guard
-      apply_rule(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc, nullptr, nullptr, s);
-      return;
-    }
-    if (ema_on()) {  // the same launch, with the shadow's update (optim_ema.hip)
-      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
-      else sgd_apply_ema(ema_args(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), beg), s);
-      return;
-    }
-    if (opt_ == 0) adam_apply(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
-    else sgd_apply(sgd_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), s);
   }
   // Adam over up to 3 ranges of the flat buffers in one launch (o: buffer bases)
   void apply_adam_ranges(const AdamArgs& o, int nr, const int64_t* beg, const int64_t* n, hipStream_t s) {
-    if (ema_on()) adam_ranges_ema(ema_args(o, 0), nr, beg, n, s);
-    else adam_apply_ranges(o, nr, beg, n, s);
+    adam_launch_ranges(o, mods(0, nullptr, nullptr), nr, beg, n, s);
   }
 
   // Full synchronous data-parallel step (the reference's SyncReplicasOptimizer global step with
@@ -567,7 +560,7 @@ class MnistEngine : public torch::CustomClassHolder {
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the global norm needs the whole aggregated gradient on every rank; use the all-reduce schedule");
     // a sharded gradient has no per-variable norm either
-    TORCH_CHECK(!(lw_ && (zero_ || sfb_active())), lw_ == 1 ? "set_lamb" : "set_lars", " conflicts with ",
+    TORCH_CHECK(!(layerwise() && (zero_ || sfb_active())), lw_ == LwKind::Lamb ? "set_lamb" : "set_lars", " conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the per-variable norms need the whole aggregated gradient on every rank; use the all-reduce schedule");
     // nor a whole-gradient sum of squares to call finite
@@ -593,7 +586,7 @@ class MnistEngine : public torch::CustomClassHolder {
       train_step_accum(dp);
       return;
     }
-    if (clip_norm_ > 0 || lw_ || guard_) {
+    if (clip_norm_ > 0 || layerwise() || guard_) {
       train_step_clip(dp);
       return;
     }
@@ -613,7 +606,7 @@ class MnistEngine : public torch::CustomClassHolder {
     MnistStepArgs a = args();
     // one GPU: nothing to overlap with. With Adam ONE kernel ends the step: it reduces the conv
     // weight-gradient slabs itself and bumps the step (its t was written by the head kernel).
-    const bool fused = opt_ == 0 && fuse_tail_;
+    const bool fused = opt_ == OptKind::Adam && fuse_tail_;
     if (fused) a.t_out = (int64_t*)tnext_.data_ptr();
     // bf16 fc-region gradients (the DP wire format): the fc backward writes 2 B and Adam reads
     // 2 B per gradient instead of 4 + 4 (13 MB less HBM traffic per step)
@@ -774,7 +767,7 @@ class MnistEngine : public torch::CustomClassHolder {
     if (shard) {
       const int64_t beg[3] = {0, OFF_WD1 + rk * zshard_, OFF_BD1};
       const int64_t end[3] = {BUCKET_SPLIT, OFF_WD1 + (rk + 1) * zshard_, TOTAL};
-      if (opt_ == 0 && BUCKET_SPLIT % 4 == 0 && zshard_ % 4 == 0) {  // one launch over the ranges
+      if (opt_ == OptKind::Adam && BUCKET_SPLIT % 4 == 0 && zshard_ % 4 == 0) {  // one launch over the ranges
         const int64_t n[3] = {end[0] - beg[0], end[1] - beg[1], end[2] - beg[2]};
         const AdamArgs o = adam_args(0, 0, bf16_comm_, scale, 0, t);  // buffer bases; n comes per range
         if (split_opt) {
@@ -824,7 +817,7 @@ class MnistEngine : public torch::CustomClassHolder {
     MnistF32Args f = args_f32();
     // one GPU + Adam: ONE tail kernel reduces the conv slabs, runs Adam over every region and bumps
     // the step (t from the head), as the bf16 step does
-    const bool fused = !dp && opt_ == 0 && fuse_tail_;
+    const bool fused = !dp && opt_ == OptKind::Adam && fuse_tail_;
     if (fused) f.t_out = (int64_t*)tnext_.data_ptr();
     mark(P_START, s);
     mnist_f32_forward(f, true, s);
@@ -847,15 +840,7 @@ class MnistEngine : public torch::CustomClassHolder {
     r.step_bump = (int64_t*)step_.data_ptr();
     mnist_conv_grad_reduce(r, s);
     mark(P_BCONV, s);
-    if (dp) {
-      hand_off(s, ev_b_, comm_stream_, "f32:ar<-slab_reduce");
-      mark(P_CA0, comm_stream_);
-      reduce_bucket(0, TOTAL, false);
-      mark(P_CA1, comm_stream_);
-      mark(P_CB0, comm_stream_);
-      mark(P_CB1, comm_stream_);
-      hand_off(comm_stream_, ev_done_, s, "f32:opt<-ar");
-    }
+    if (dp) all_reduce_whole(s, "f32:ar<-slab_reduce", "f32:opt<-ar", false);
     apply_optimizer_range(0, TOTAL, 1.0 / (double)world(), 0, s);
     mark(P_OPT, s);
   }
@@ -898,16 +883,7 @@ class MnistEngine : public torch::CustomClassHolder {
       mnist_conv_grad_reduce(a, s);
       tag("slab_reduce", s);
       mark(P_BCONV, s);
-      if (dp) {
-        hand_off(s, ev_b_, comm_stream_, "ar<-slab_reduce");
-        mark(P_CA0, comm_stream_);
-        reduce_bucket(0, TOTAL, false);
-        tag("ar", comm_stream_);
-        mark(P_CA1, comm_stream_);
-        mark(P_CB0, comm_stream_);
-        mark(P_CB1, comm_stream_);
-        hand_off(comm_stream_, ev_done_, s, "grad_norm<-ar");
-      }
+      if (dp) all_reduce_whole(s, "ar<-slab_reduce", "grad_norm<-ar", true);
     } else {
       if (dp) set_dp_outputs(a, bf);
       else a.step_bump = step;
@@ -937,7 +913,7 @@ class MnistEngine : public torch::CustomClassHolder {
         mark(P_BCONV, s);
       }
     }
-    whole_gradient_tail(bf, scale, s);
+    whole_gradient_tail(scale, s);
   }
 
   // The end of the steps that hold the whole aggregated gradient in one flat buffer (train_step_clip,
@@ -947,54 +923,24 @@ class MnistEngine : public torch::CustomClassHolder {
   // exactly 1 without clipping) and the optimizer its guarded instantiation, which stores nothing when
   // ok == 0. In DP the buffer is the all-reduced one, so every rank decides alike: whether a sum is
   // finite does not depend on its order.
-  void whole_gradient_tail(bool bf, double scale, hipStream_t s) {
-    const int64_t* step = (const int64_t*)step_.data_ptr();
+  void whole_gradient_tail(double scale, hipStream_t s) {
+    const bool bf = bf16_comm_ && dp();  // what both callers hold, and what apply_optimizer_range derives
     float* pair = (float*)gnorm_.data_ptr();
     float* part = (float*)gpart_.data_ptr();
-    const float* gscale = nullptr;  // the step's clip factor on the device; none without clipping
-    if (guard_) {
+    if (guard_ || clip_norm_ > 0)
       grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
+    if (guard_) {
       grad_guard_finish(part, grad_norm_blocks(TOTAL), (float)scale,
                         clip_norm_ > 0 ? (float)clip_norm_ : std::numeric_limits<float>::infinity(), pair,
                         (int64_t*)skipped_.data_ptr(), s);
       tag("grad_guard", s);
-      gscale = pair + 1;
-      const float* ok = pair + 2;
-      if (lw_) {
-        apply_layerwise(bf, scale, 0, step, gscale, s, ok);
-      } else if (opt_ >= 3) {
-        apply_rule(0, TOTAL, bf, scale, 0, step, gscale, ok, s);
-      } else if (ema_on()) {
-        if (opt_ == 0) adam_apply_guard(AdamEmaGuardArgs{ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
-        else sgd_apply_guard(SgdEmaGuardArgs{ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), ok}, s);
-      } else {
-        if (opt_ == 0) adam_apply_guard(AdamGuardArgs{AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), gscale}, ok}, s);
-        else sgd_apply_guard(SgdGuardArgs{SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), gscale}, ok}, s);
-      }
-      tag("opt", s);
-      mark(P_OPT, s);
-      return;
-    }
-    if (clip_norm_ > 0) {
-      grad_sumsq((const float*)grad_.data_ptr(), bf ? (const uint16_t*)gbf_.data_ptr() : nullptr, TOTAL, part, s);
+    } else if (clip_norm_ > 0) {
       grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
       tag("grad_norm", s);
-      gscale = pair + 1;
     }
-    if (lw_) {
-      apply_layerwise(bf, scale, 0, step, gscale, s);
-    } else if (opt_ >= 3) {
-      apply_rule(0, TOTAL, bf, scale, 0, step, gscale, nullptr, s);
-    } else if (ema_on()) {
-      if (opt_ == 0) adam_apply_ema(ema_args(adam_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
-      else sgd_apply_ema(ema_args(sgd_args(0, TOTAL, bf, scale, 0, step), 0, gscale), s);
-    } else if (gscale) {
-      if (opt_ == 0) adam_apply_clip(AdamClipArgs{adam_args(0, TOTAL, bf, scale, 0, step), gscale}, s);
-      else sgd_apply_clip(SgdClipArgs{sgd_args(0, TOTAL, bf, scale, 0, step), gscale}, s);
-    } else {
-      if (opt_ == 0) adam_apply(adam_args(0, TOTAL, bf, scale, 0, step), s);
-      else sgd_apply(sgd_args(0, TOTAL, bf, scale, 0, step), s);
-    }
+    // the step's clip factor and the guard's ok on the device; null without
+    apply_optimizer_range(0, TOTAL, scale, 0, s, nullptr, guard_ || clip_norm_ > 0 ? pair + 1 : nullptr,
+                          guard_ ? pair + 2 : nullptr);
     tag("opt", s);
     mark(P_OPT, s);
   }
@@ -1073,14 +1019,7 @@ class MnistEngine : public torch::CustomClassHolder {
       mark(P_BCONV, s);
     } else if (fp32_) {
       mark(P_BCONV, s);
-      hand_off(s, ev_b_, comm_stream_, "ar<-accum");
-      mark(P_CA0, comm_stream_);
-      reduce_bucket(0, TOTAL, false);
-      tag("ar", comm_stream_);
-      mark(P_CA1, comm_stream_);
-      mark(P_CB0, comm_stream_);
-      mark(P_CB1, comm_stream_);
-      hand_off(comm_stream_, ev_done_, s, "grad_norm<-ar");
+      all_reduce_whole(s, "ar<-accum", "grad_norm<-ar", true);
     } else {
       hand_off(s, ev_a_, comm_stream_, "ar_fc<-accum");
       mark(P_CA0, comm_stream_);
@@ -1090,7 +1029,7 @@ class MnistEngine : public torch::CustomClassHolder {
       all_reduce_conv(s, bf);  // behind bucket A's on the comm stream: ev_done_ covers both
       wait(s, ev_done_, "grad_norm<-ar_conv");
     }
-    whole_gradient_tail(bf, scale, s);
+    whole_gradient_tail(scale, s);
   }
 
   void train_step_zero() {
@@ -1371,6 +1310,18 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_CB1, comm_stream_);
     HIP_OK(hipEventRecord(ev_done_, comm_stream_));
   }
+  // fp32 DP steps: ONE all-reduce of the whole fp32 buffer on the comm stream, behind what `s` has queued
+  // (edge `in`); `s` goes on behind it (edge `out`). One bucket, so bucket B's marks time nothing.
+  void all_reduce_whole(hipStream_t s, const char* in, const char* out, bool tagged) {
+    hand_off(s, ev_b_, comm_stream_, in);
+    mark(P_CA0, comm_stream_);
+    reduce_bucket(0, TOTAL, false);
+    if (tagged) tag("ar", comm_stream_);
+    mark(P_CA1, comm_stream_);
+    mark(P_CB0, comm_stream_);
+    mark(P_CB1, comm_stream_);
+    hand_off(comm_stream_, ev_done_, s, out);
+  }
 
   // ---- argument structs of the optimizer kernels: each is filled in one place ----
   // Range [beg, beg + n) of the flat buffers; bf_grads: the gradients are bf16 in gbf_
@@ -1381,7 +1332,7 @@ class MnistEngine : public torch::CustomClassHolder {
                     (float)b2_, (float)eps_, t, t_offset, (float)grad_scale};
   }
   SgdArgs sgd_args(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t) {
-    return SgdArgs{(float*)params_.data_ptr() + beg, opt_ == 2 ? (float*)m_.data_ptr() + beg : nullptr,
+    return SgdArgs{(float*)params_.data_ptr() + beg, opt_ == OptKind::Momentum ? (float*)m_.data_ptr() + beg : nullptr,
                    (const float*)grad_.data_ptr() + beg, (uint16_t*)pbf_.data_ptr() + beg,
                    bf_grads ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr, n, sched_, (float)momentum_, 0.f,
                    (float)grad_scale, nesterov_ ? 1 : 0, t, t_offset};
@@ -1393,9 +1344,12 @@ class MnistEngine : public torch::CustomClassHolder {
                          (float)b1_, (float)b2_, (float)eps_, (const int64_t*)tnext_.data_ptr(),
                          (int64_t*)step_.data_ptr(), bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr};
   }
+  // what every optimizer setter ends with: the rule, no layer-wise form, a constant rate
+  void set_optimizer(OptKind kind, double lr) { opt_ = kind; lw_ = LwKind::None; sched_ = lr_constant((float)lr); }
+  bool layerwise() const { return lw_ != LwKind::None; }
   // ---- layer-wise optimizers ----
   // the variable table of the flat layout and its block table, built once, on the device
-  void set_layerwise(int kind, bool skip_bias) {
+  void set_layerwise(LwKind kind, bool skip_bias) {
     const int w = LW_DECAY | LW_ADAPT, b = skip_bias ? 0 : w;
     const LwSegment segs[8] = {{OFF_WC1, KTAPS * C1, w}, {OFF_BC1, C1, b}, {OFF_WC2, KTAPS * C1 * C2, w}, {OFF_BC2, C2, b},
                                {OFF_WD1, (int64_t)FEAT * HID, w}, {OFF_BD1, HID, b}, {OFF_OUT, HID * NCLS, w},
@@ -1423,17 +1377,15 @@ class MnistEngine : public torch::CustomClassHolder {
       lw_part_ = at::empty({lw_nblocks_, 2}, params_.options());  // every entry is stored by every stage 1
       lw_out_ = at::zeros({8, 3}, at::kFloat).to(params_.device());
     }
-    if (!one_.defined()) one_ = at::ones({1}, at::kFloat).to(params_.device());  // the clip factor without clipping
     lw_ = kind;
   }
-  // stages 1, 2, 3 over [0, TOTAL); gscale: the step's clip factor on the device, null without clipping
-  // ok: the non-finite guard's device ok, null without the guard
-  void apply_layerwise(bool bf_grads, double grad_scale, int t_offset, const int64_t* t, const float* gscale,
-                       hipStream_t s, const float* ok = nullptr) {
+  // stages 1, 2, 3 over [0, TOTAL); m: the step's modifiers (mods(0, ...))
+  void apply_layerwise(bool bf_grads, double grad_scale, int t_offset, const int64_t* t, const OptMods& m, hipStream_t s) {
+    const bool lamb = lw_ == LwKind::Lamb;
     LayerwiseArgs a{};
     a.p = (float*)params_.data_ptr();
     a.s1 = (float*)m_.data_ptr();
-    a.s2 = lw_ == 1 ? (float*)v_.data_ptr() : nullptr;
+    a.s2 = lamb ? (float*)v_.data_ptr() : nullptr;
     a.g = bf_grads ? nullptr : (const float*)grad_.data_ptr();
     a.gbf = bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr;
     a.pbf = (uint16_t*)pbf_.data_ptr();
@@ -1448,31 +1400,25 @@ class MnistEngine : public torch::CustomClassHolder {
     a.beta2 = (float)b2_;
     a.momentum = (float)momentum_;
     a.eeta = (float)lw_eeta_;
-    a.eps = (float)(lw_ == 1 ? eps_ : lw_eps_);
+    a.eps = (float)(lamb ? eps_ : lw_eps_);
     a.weight_decay = (float)lw_wd_;
     a.step = t;
     a.t_offset = t_offset;
     a.grad_scale = (float)grad_scale;
-    a.gscale = gscale ? gscale : (const float*)one_.data_ptr();
-    a.ok = ok;
-    if (ema_on()) {
-      ema_bf_stale_ = true;
-      a.ema = (float*)ema_.data_ptr();
-      a.ema_decay = (float)ema_decay_;
-      a.ema_num_updates = ema_nu_ ? 1 : 0;
-    }
-    if (lw_ == 1) lamb_apply(a, s);
+    apply_mods(a, m);
+    if (lamb) lamb_apply(a, s);
     else lars_apply(a, s);
   }
-  // RMSProp / Adagrad over [beg, beg + n); gscale: the step's clip factor on the device, null without
-  // clipping; ok: the non-finite guard's device ok, null without the guard
+  // RMSProp / Adagrad over [beg, beg + n); m: the range's modifiers (mods(beg, ...))
+  bool is_rule() const { return opt_ == OptKind::RmsProp || opt_ == OptKind::Adagrad; }
   void apply_rule(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t,
-                  const float* gscale, const float* ok, hipStream_t s) {
+                  const OptMods& m, hipStream_t s) {
+    const bool rms = opt_ == OptKind::RmsProp;
     RuleArgs a{};
     a.p = (float*)params_.data_ptr() + beg;
     a.s1 = (float*)v_.data_ptr() + beg;
-    a.s2 = opt_ == 3 ? (float*)m_.data_ptr() + beg : nullptr;
-    a.s3 = opt_ == 3 && centered_ ? (float*)s3_.data_ptr() + beg : nullptr;
+    a.s2 = rms ? (float*)m_.data_ptr() + beg : nullptr;
+    a.s3 = rms && centered_ ? (float*)s3_.data_ptr() + beg : nullptr;
     a.g = bf_grads ? nullptr : (const float*)grad_.data_ptr() + beg;
     a.gbf = bf_grads ? (const uint16_t*)gbf_.data_ptr() + beg : nullptr;
     a.pbf = (uint16_t*)pbf_.data_ptr() + beg;
@@ -1484,31 +1430,26 @@ class MnistEngine : public torch::CustomClassHolder {
     a.step = t;
     a.t_offset = t_offset;
     a.grad_scale = (float)grad_scale;
-    a.gscale = gscale ? gscale : (const float*)one_.data_ptr();
-    a.ok = ok;
-    if (ema_on()) {
-      ema_bf_stale_ = true;
-      a.ema = (float*)ema_.data_ptr() + beg;
-      a.ema_decay = (float)ema_decay_;
-      a.ema_num_updates = ema_nu_ ? 1 : 0;
-    }
-    if (opt_ == 3) rmsprop_apply(a, centered_, s);
+    apply_mods(a, m);
+    if (rms) rmsprop_apply(a, centered_, s);
     else adagrad_apply(a, s);
   }
-  // The EMA variants' arguments (set_ema): the clip wrapper -- gscale the step's clip factor, or a
-  // device 1.0f without clipping -- and the shadow at the range's start. Each marks the bf16 image of
-  // the shadow stale: an EMA launch is about to move the shadow.
+  // What a step adds to the bare update over a range that starts at beg (optim_launch.h). The only reader of
+  // the EMA settings and one_ for a flat launch; with the shadow it marks the shadow's bf16 image stale: an
+  // EMA launch is about to move the shadow.
   bool ema_on() const { return ema_decay_ > 0; }
-  AdamEmaArgs ema_args(const AdamArgs& a, int64_t beg, const float* gscale = nullptr) {
-    ema_bf_stale_ = true;
-    return AdamEmaArgs{AdamClipArgs{a, gscale ? gscale : (const float*)one_.data_ptr()}, (float*)ema_.data_ptr() + beg,
-                       (float)ema_decay_, ema_nu_ ? 1 : 0};
+  OptMods mods(int64_t beg, const float* gscale, const float* ok) {
+    OptMods m{gscale, ok};
+    m.one = (const float*)one_.data_ptr();
+    if (ema_on()) {
+      ema_bf_stale_ = true;
+      m.ema = (float*)ema_.data_ptr() + beg;
+      m.ema_decay = (float)ema_decay_;
+      m.ema_num_updates = ema_nu_ ? 1 : 0;
+    }
+    return m;
   }
-  SgdEmaArgs ema_args(const SgdArgs& a, int64_t beg, const float* gscale = nullptr) {
-    ema_bf_stale_ = true;
-    return SgdEmaArgs{SgdClipArgs{a, gscale ? gscale : (const float*)one_.data_ptr()}, (float*)ema_.data_ptr() + beg,
-                      (float)ema_decay_, ema_nu_ ? 1 : 0};
-  }
+  // the fused one-GPU tail's EMA wrapper
   MnistAdamEmaArgs ema_args(const MnistAdamArgs& o) {
     ema_bf_stale_ = true;
     return MnistAdamEmaArgs{o, (float*)ema_.data_ptr(), (float)ema_decay_, ema_nu_ ? 1 : 0};
@@ -1726,13 +1667,13 @@ class MnistEngine : public torch::CustomClassHolder {
   uint32_t seed_, rank_;
   int fc1_splits_, wg2_splits_;
   int64_t input_mode_ = 0;
-  int opt_ = 0;  // 0 Adam (LAMB), 1 GradientDescent, 2 Momentum (LARS), 3 RMSProp, 4 Adagrad
+  OptKind opt_ = OptKind::Adam;
   // RMSProp / Adagrad (set_rmsprop / set_adagrad): the rule's scalars and the centered rule's third slot
   double rule_decay_ = 0.9, rule_eps_ = 1e-10;
   bool centered_ = false;
   at::Tensor s3_;
-  // layer-wise optimizer (set_lamb / set_lars): 0 = off, 1 = LAMB, 2 = LARS; its tables and outputs
-  int lw_ = 0, lw_nblocks_ = 0;
+  LwKind lw_ = LwKind::None;  // layer-wise optimizer (set_lamb / set_lars); its tables and outputs
+  int lw_nblocks_ = 0;
   double lw_wd_ = 0.0, lw_eeta_ = 0.0, lw_eps_ = 0.0;
   at::Tensor lw_blocks_, lw_segs_, lw_part_, lw_out_;
   double b1_ = 0.9, b2_ = 0.999, eps_ = 1e-8, momentum_ = 0.0;
@@ -1779,7 +1720,7 @@ class MnistEngine : public torch::CustomClassHolder {
   int64_t accum_ = 1;
   at::Tensor acc_, micro_;
   // moving average of the weights (set_ema): 0 = off; the fp32 shadow, its bf16 image for
-  // evaluate(use_ema) (cast when stale) and the device 1.0f the EMA variants read as their clip factor
+  // evaluate(use_ema) (cast when stale); one_: the device 1.0f of OptMods::one
   double ema_decay_ = 0.0;
   bool ema_nu_ = false;
   at::Tensor ema_, ema_bf_, one_;
