@@ -22,6 +22,10 @@ channel, a 64-row tile, one image, ...), and an elementwise ``max|got - ref| / R
 ``floor = RMS(ref) * sqrt(slice size) * FLOOR_FRAC`` makes the check on a dead slice (all-zero
 reference) an absolute one. Bounds: one number per (dtype, tensor, slicing), 3x the worst value
 measured on the kernels (profiles/mnist_oracle_slices_r7.txt).
+
+The last section runs the fused one-GPU Adam step, whose gradient is never stored, reads the gradient it
+consumed back out of Adam's m and puts it through the same checker (tests/test_mnist_fused_step_gpu.py,
+tests/test_mnist_fused_step_checker_cpu.py, tools/mnist_oracle_rel.py --fused).
 """
 from __future__ import annotations
 
@@ -494,3 +498,227 @@ def collect(eng, backward=True, train=True):
         got["dlogits"] = eng.dlogits().double().cpu()
         got["dh"] = eng.dhidden().double().cpu()
     return got
+
+
+# ------------------------------------------------------------------ the fused one-GPU step
+# train_step() with set_fused_tail(1) ends in ONE launch (mnist_adam_kernel, csrc/mnist_tail.h) that sums
+# the conv weight-gradient slabs, reads the fc-region gradient (bf16 with set_local_bf16_grads) and
+# applies Adam: the gradient it consumes is never stored. It is read back out of Adam's m instead
+# (grads_from_adam_m) and goes through the same per-slice checker as the unfused step's grads().
+#
+# The batches of tests/test_mnist_fused_step_gpu.py, on the edges of the tail's slab loops. conv1:
+# 2 B slabs, a pass of slab_sum<16> takes 16 x 16 = 256, thread group q sums slabs q, q + 16, ...;
+# conv2: ceil(B / 4) slabs (bf16) or ceil(B / 2) (fp32), a pass of slab_sum<4> takes 4 x 16 = 64.
+#   1, 2, 3, 5: 2, 4, 6, 10 conv1 slabs for 16 q groups, 1 .. 3 conv2 slabs for 4; B = 1, 2, 3, 5 (bf16)
+#       and 1, 3, 5 (fp32) leave the last conv2 image group half filled;
+#   37: prime -- 74 conv1 slabs (q groups with 5 and with 4 slabs), 10 / 19 conv2 slabs;
+#   65: 130 conv1 slabs; fp32: 33 conv2 slabs, the last holding one image;
+#   130: 260 conv1 slabs = one full pass and a second of 4; fp32: 65 conv2 slabs = a second pass of one;
+#   258 (bf16 only): 516 conv1 slabs = two full passes and 4; 65 conv2 slabs = a second pass of one, half
+#       filled.
+FUSED_BATCHES = {"bf16": (1, 2, 3, 5, 37, 65, 130, 258), "fp32": (1, 2, 3, 5, 37, 65, 130)}
+FC_GRADS = ("wd1", "bd1", "out", "out_b")
+# The scheduled and the EMA instantiations' settings: set_lr_schedule's (kind, [lr, decay_steps, rate, end,
+# power, alpha, warmup_steps, staircase], boundaries, values) -- lr = 1e-4 * 0.5^s -- and set_ema's (decay,
+# num_updates). They run at global step 1, where the schedule's rate is not its base rate, so one Adam
+# step precedes the checked one, and the rate is small for that step's sake: at 0.01 it moves every
+# parameter of the B = 3 case by 0.01 the same way for all three images, the logits reach +-45, and there
+# the fp32 step -- fused and unfused alike, they agree to 2.5e-8 -- is up to 1.8e-4 from the oracle, 11x a
+# bound calibrated on logits of order 1 (profiles/mnist_fused_step_slices.txt, last section).
+FUSED_LR = 1e-4
+FUSED_SCHEDULE = ("exponential", [FUSED_LR, 1.0, 0.5, 0.0, 1.0, 0.0, 0.0, 0.0], [], [])
+FUSED_EMA = (0.99, True)
+# Classes of the fused step whose bound is not BOUNDS + allowance: 3x the value measured on the fused
+# path against the oracle, each cited to profiles/mnist_fused_step_slices.txt. (None was needed.)
+FUSED_BOUNDS = {"bf16": {}, "fp32": {}}
+
+
+def _f32(v):
+    """The fp32 value the kernel holds for a host double, as a Python float."""
+    return float(np.float32(v))
+
+
+def run_fused_step(dev, dtype, params, x, y, keep=1.0, *, local_bf16=False, dataset=False, schedule=None, ema=None,
+                   step0=0, b1=0.9, b2=0.999, lr=0.01, eps=1e-8):
+    """One fused one-GPU Adam step (set_fused_tail(1)) of the native engine from m = v = 0, at global
+    step ``step0``, on the rows ``x, y``; everything needed to check it afterwards.
+
+    params: dict of tensors. schedule: the (kind, params, boundaries, values) of set_lr_schedule or None.
+    ema: (decay, num_updates) or None. dataset=True: the rows come from a device dataset of
+    n = 2 B + 3 rows through a fixed non-identity permutation (so the cursor wraps at step 1); the
+    dataset is laid out so that step ``step0`` draws exactly ``x, y`` -- row perm[(step0 B + b) % n]
+    holds x[b] -- and the other rows are random. step0 > 0: that many ordinary fused steps run first (feed
+    mode: on the same x, y), then m and v are zeroed in place on the same stream; the step counter, the
+    dropout key, Adam's t and the data cursor stay advanced.
+
+    Returns a dict: p_before, p_after, m_after, v_after (fp32, CPU), params_bf16_before / params_bf16,
+    ema_before / ema_after (None without EMA), step (step_tensor() after), t = step0 + 1, lr (the fp32
+    rate of this update, lr_at_step(step0)), ema_decay (ema_decay_at_step(t)), b1 / b2 / eps, x / y (the
+    rows the step used: read back through perm in dataset mode), acts (collect(eng, backward=False))."""
+    from tensorflow_distributed_amd import _native
+
+    _native.require()
+    B = x.shape[0]
+    eng = torch.classes.tfd.MnistEngine(B, dev.index or 0, keep, 1234, 0)
+    eng.set_dtype(dtype)
+    eng.set_adam(lr, b1, b2, eps)
+    eng.set_fused_tail(1)
+    eng.set_local_bf16_grads(1 if local_bf16 else 0)
+    if schedule is not None:
+        eng.set_lr_schedule(*schedule)
+    yi = torch.as_tensor(y).to(torch.int32)
+    if dataset:
+        n = 2 * B + 3
+        g = torch.Generator().manual_seed(11)
+        data = torch.rand(n, 784, generator=g)
+        labels = torch.randint(0, 10, (n,), generator=g, dtype=torch.int32)
+        perm = torch.randperm(n, generator=g)
+        assert not torch.equal(perm, torch.arange(n))
+        used = perm[(step0 * B + torch.arange(B)) % n]
+        data[used] = x.to(torch.float32)
+        labels[used] = yi
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        eng.params().copy_(M.flat_from_dict(params).to(dev))
+        eng.sync_shadow()
+        if ema is not None:
+            eng.set_ema(float(ema[0]), bool(ema[1]))  # copies the parameters into the shadow
+        if dataset:
+            eng.set_dataset(data.to(dev), labels.to(dev), perm.to(torch.int32).to(dev))
+            eng.set_input_mode(1)
+        else:
+            eng.feed_x().copy_(x.to(torch.float32).to(dev))
+            eng.feed_y().copy_(yi.to(dev))
+        for _ in range(step0):
+            eng.train_step()
+        if step0:
+            eng.adam_m().zero_()
+            eng.adam_v().zero_()
+        res = {
+            "p_before": eng.params().clone(), "params_bf16_before": eng.params_bf16().clone(),
+            "ema_before": eng.ema_params().clone() if ema is not None else None,
+        }
+        eng.train_step()
+    torch.cuda.synchronize()
+    res = {k: (v.cpu() if v is not None else None) for k, v in res.items()}
+    t = step0 + 1
+    res.update(
+        p_after=eng.params().cpu(), m_after=eng.adam_m().cpu(), v_after=eng.adam_v().cpu(),
+        params_bf16=eng.params_bf16().cpu(), ema_after=eng.ema_params().cpu() if ema is not None else None,
+        step=int(eng.step_tensor().item()), t=t, lr=float(eng.lr_at_step(step0)),
+        ema_decay=float(eng.ema_decay_at_step(t)) if ema is not None else None,
+        b1=b1, b2=b2, eps=eps, acts=collect(eng, backward=False),
+    )
+    if dataset:
+        res["x"], res["y"] = data[used].clone(), labels[used].clone()
+    else:
+        res["x"], res["y"] = x.to(torch.float32).clone(), yi.clone()
+    return res
+
+
+def grads_from_adam_m(m_after, b1=0.9):
+    """The gradient a step that started from m = 0 consumed, fp64 on the CPU: the tail writes
+    m' = m + (g - m) * c1 = g * c1 with c1 = 1.f - beta1 (exact in fp32 for beta1 in [0.5, 1]), ONE fp32
+    rounding, so m' / c1 is g to within 2^-24 relative per element -- in every region, whatever the
+    order the slabs were summed in."""
+    c1 = float(np.float32(1.0) - np.float32(b1))
+    return torch.as_tensor(m_after).detach().cpu().to(torch.float64) / c1
+
+
+def fused_allowance(key, ref, dtype, local_bf16):
+    """What check_fused adds to bound_for(key, ref, dtype). Derived from the number formats, not
+    measured:
+
+      the recovery  g_used = m' / c1 carries the one fp32 rounding of g * c1: |g_used - g| <= 2^-24 |g|
+                    per element. Over any slice that is a relative L2 error <= 2^-24; an element is off by
+                    <= 2^-24 max|g|, which the "elem" measure divides by RMS(g). Both doubled: 2^-23 and
+                    2^-23 max|g| / RMS(g).
+      local_bf16    the fc backward stores the fc-region gradient (wd1, bd1, out, out_b) as bf16 and the
+                    tail reads that: one round-to-nearest to 8 significant bits, <= 2^-9 |g| per element,
+                    so <= 2^-9 relative L2 per slice and <= 2^-9 max|g| for an element. Doubled: 2^-8 and
+                    2^-8 max|g| / RMS(g). (bf16 dtype only: the fp32 step has no such option.)
+
+    Everything that is not a gradient gets 0."""
+    t, s = key
+    if t not in GRADS:
+        return 0.0
+    g = ref["grads"][t]
+    peak = g.abs().max().item() / _rms(g) if s == "elem" else 1.0
+    a = 2.0 ** -23 * peak
+    if local_bf16 and t in FC_GRADS:
+        a += 2.0 ** -8 * peak
+    return a
+
+
+def fused_bound_for(key, ref, dtype, local_bf16):
+    """The bound of one class on the fused step: FUSED_BOUNDS where the class has an entry (with the
+    softmax allowance bound_for adds), else bound_for; plus fused_allowance."""
+    base = bound_for(key, ref, dtype)
+    if key in FUSED_BOUNDS[dtype]:
+        base += FUSED_BOUNDS[dtype][key] - (BOUNDS[dtype][key] or ZERO_FLOOR[dtype])
+    return base + fused_allowance(key, ref, dtype, local_bf16)
+
+
+def fused_got(res):
+    """A fused step's result (run_fused_step) in ``measure``'s format: the forward's activations plus
+    the gradient the tail consumed, split per tensor."""
+    got = dict(res["acts"])
+    got["grads"] = {k: v.clone() for k, v in M.dict_from_flat(grads_from_adam_m(res["m_after"], res["b1"])).items()}
+    return got
+
+
+def fused_oracle(res, dtype, keep=1.0, step=0):
+    """The oracle's step on what the fused step read: p_before, the rows it used, the dropout mask of
+    global step ``step``, the kernel's side of near ties (``follow``)."""
+    B = res["x"].shape[0]
+    mask = M.native_dropout_mask(B, step, 0, 1234, keep) if keep < 1.0 else None
+    params = {k: v.clone() for k, v in M.dict_from_flat(res["p_before"]).items()}
+    return oracle_step(params, res["x"], res["y"], dtype, keep, mask, follow=res["acts"])
+
+
+def measure_fused(res, ref, dtype, local_bf16, only=None):
+    """{(tensor, slicing): (error, bound, index)} of every class of the fused step (all of them, passing
+    or not)."""
+    out = {}
+    for key, (e, i) in measure(fused_got(res), ref).items():
+        if only is None or key[0] in only:
+            out[key] = (e, fused_bound_for(key, ref, dtype, local_bf16), i)
+    return out
+
+
+def check_fused(res, ref, dtype, local_bf16, only=None):
+    """``check`` for a fused step: the classes above bound_for + fused_allowance, in the same
+    {(tensor, slicing): (error, bound, index)} shape. Empty when the step passes."""
+    return {k: v for k, v in measure_fused(res, ref, dtype, local_bf16, only).items() if not v[0] <= v[1]}
+
+
+def adam_reference(p_before, g_used, t, lr, b1=0.9, b2=0.999, eps=1e-8):
+    """fp64 (m, v, p') of TF's ApplyAdam from m = v = 0:  m = g (1 - b1), v = g^2 (1 - b2),
+    p' = p - lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps).  b1, b2, eps and lr are rounded to the
+    fp32 values the kernel holds (pass lr = lr_at_step(t - 1) under a schedule); t = step0 + 1."""
+    b1, b2, eps, lr = _f32(b1), _f32(b2), _f32(eps), _f32(lr)
+    p = torch.as_tensor(p_before).detach().cpu().to(torch.float64)
+    g = torch.as_tensor(g_used).to(torch.float64)
+    m = g * (1.0 - b1)
+    v = g * g * (1.0 - b2)
+    lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+    return m, v, p - lr_t * m / (v.sqrt() + eps)
+
+
+FP32_TINY = 2.0 ** -126  # the smallest normal fp32 number: below it a product has no relative precision
+
+
+def update_ratios(res):
+    """The fused step's v and p' against adam_reference from its own consumed gradient, as the worst
+    ratios error / tolerance (<= 1 passes):
+      v   |v - v_ref| <= 2^-22 v_ref (+ FP32_TINY: g * g below the normal range is flushed or rounded
+          with no relative precision; such a v is 1e-30 of sqrt's eps-sized partner in the update);
+      p   |p' - p_ref| <= 2^-24 |p_ref| + 2^-18 |p_ref - p_before|."""
+    g = grads_from_adam_m(res["m_after"], res["b1"])
+    _, v_ref, p_ref = adam_reference(res["p_before"], g, res["t"], res["lr"], res["b1"], res["b2"], res["eps"])
+    v, p, p0 = res["v_after"].double(), res["p_after"].double(), res["p_before"].double()
+    rv = (v - v_ref).abs() / (2.0 ** -22 * v_ref + FP32_TINY)
+    rp = (p - p_ref).abs() / (2.0 ** -24 * p_ref.abs() + 2.0 ** -18 * (p_ref - p0).abs()).clamp_min(1e-300)
+    rp = torch.where(p == p_ref, torch.zeros_like(rp), rp)
+    iv, ip = int(rv.argmax()), int(rp.argmax())
+    return {"v": (rv[iv].item(), iv), "p": (rp[ip].item(), ip)}

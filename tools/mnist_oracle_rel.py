@@ -11,7 +11,14 @@ B = 37 dropout case at three seeds each, then the special-input cases of
 tests/test_mnist_kernel_edges_gpu.py (reported, not part of the bounds). The last section is the
 BOUNDS table of tests/mnist_oracle.py: 3x the worst of each class.
 
-    python tools/mnist_oracle_rel.py [--seeds 0,1,2] [--slices]
+--fused: the fused one-GPU Adam step (train_step() with set_fused_tail(1)) over the cases of
+tests/test_mnist_fused_step_gpu.py: the gradient the tail consumed, read back out of Adam's m, per
+slice against the fp64 oracle -- per dtype, setting and class the measured error and the bound used
+(BOUNDS plus the derived allowances of tests/mnist_oracle.py::fused_allowance) -- and the worst ratios
+error / tolerance of v and p' against fp64 ApplyAdam from that gradient. Its output is
+profiles/mnist_fused_step_slices.txt.
+
+    python tools/mnist_oracle_rel.py [--seeds 0,1,2] [--slices | --fused]
 """
 import argparse
 import os
@@ -106,16 +113,92 @@ def slices(seeds, dev):
         print(f"bound {dtype} {t} {s} {e:.3e} [{name}] {3 * e:.3e}")
 
 
+def fused(dev):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mnist_oracle as O
+
+    worst = {}
+    ratios = {}
+
+    def run(name, dtype, B, keep=1.0, local_bf16=False, step0=0, update=False, **kw):
+        res = O.run_fused_step(dev, dtype, *O.random_case(B), keep=keep, local_bf16=local_bf16, step0=step0, **kw)
+        ref = O.fused_oracle(res, dtype, keep, step0)
+        bf = local_bf16 and dtype == "bf16"
+        table = O.measure_fused(res, ref, dtype, bf, only=O.GRADS)
+        by = {}
+        for (t, s), (e, b, i) in sorted(table.items()):
+            by.setdefault(t, []).append(f"{s}={e:.2e}/{b:.2e}@{i}{'' if e <= b else ' ABOVE'}")
+            w = worst.get((dtype, bf, (t, s)), (-1.0, 0.0, ""))
+            if e / b > w[0]:
+                worst[(dtype, bf, (t, s))] = (e / b, e, f"{name} B={B}")
+        for t, parts in by.items():
+            print(f"{dtype} {name} B={B} {t}: " + " ".join(parts), flush=True)
+        if update:
+            r = O.update_ratios(res)
+            print(f"{dtype} {name} B={B} update t={res['t']}: v ratio {r['v'][0]:.3f}@{r['v'][1]} "
+                  f"p ratio {r['p'][0]:.3f}@{r['p'][1]}", flush=True)
+            for k in ("v", "p"):
+                ratios[(dtype, k)] = max(ratios.get((dtype, k), 0.0), r[k][0])
+
+    print("# fused one-GPU Adam step: class=error/bound@worst index; bound = BOUNDS + fused_allowance")
+    print("# consumed gradient: feed mode, keep 1, fp32 fc gradients")
+    for dtype in ("bf16", "fp32"):
+        for B in O.FUSED_BATCHES[dtype]:
+            run("edge", dtype, B)
+    print("# the benchmark's settings: bf16, bf16 fc gradients, dataset mode, keep 0.75")
+    for B in (5, 37, 130):
+        run("bench", "bf16", B, keep=0.75, local_bf16=True, dataset=True)
+    print("# later steps: global step 2, dataset mode, keep 0.75")
+    for dtype in ("bf16", "fp32"):
+        run("step2", dtype, 37, keep=0.75, dataset=True, step0=2)
+    print("# tail instantiations at global step 1: lr 1e-4, schedule lr 1e-4 * 0.5^s, EMA 0.99 with num_updates")
+    for variant in ("sched", "ema", "sched+ema"):
+        for dtype in ("bf16", "fp32"):
+            for B in (3, 130):
+                run(variant, dtype, B, step0=1, update=True, lr=O.FUSED_LR, schedule=O.FUSED_SCHEDULE if "sched" in variant else None,
+                    ema=O.FUSED_EMA if "ema" in variant else None)
+    print("# update from the consumed gradient: B = 37, dataset mode, keep 0.75; ratios are error / tolerance")
+    for step0 in (0, 2):
+        for dtype in ("bf16", "fp32"):
+            for lb in (False, True):
+                run(f"update step0={step0} local_bf16={int(lb)}", dtype, 37, keep=0.75, local_bf16=lb, dataset=True,
+                    step0=step0, update=True)
+    print("# not part of the tests: the fp32 B = 3 case at global step 1 after one step at lr 0.01 (logits +-45), the fused")
+    print("# step and the unfused kernels at the same parameters (see FUSED_LR in tests/mnist_oracle.py)")
+    res = O.run_fused_step(dev, "fp32", *O.random_case(3), step0=1)
+    ref = O.fused_oracle(res, "fp32", 1.0, 1)
+    pd = {k: v.clone() for k, v in M.dict_from_flat(res["p_before"]).items()}
+    got = O.run_engine(dev, "fp32", pd, res["x"], res["y"])
+    m_un = O.measure(got, O.oracle_step(pd, res["x"], res["y"], "fp32", follow=got))
+    gu = O.fused_got(res)["grads"]
+    print(f"max |logit| {ref['logits'].abs().max().item():.1f}")
+    for (t, s), (e, b, i) in sorted(O.measure_fused(res, ref, "fp32", False, only=O.GRADS).items()):
+        print(f"fp32 lr=0.01 B=3 {t} {s}: fused {e:.2e} unfused {m_un[(t, s)][0]:.2e} bound {b:.2e}")
+    for t in O.GRADS:
+        print(f"fp32 lr=0.01 B=3 {t}: |fused - unfused| / |unfused| = "
+              f"{((gu[t] - got['grads'][t]).norm() / got['grads'][t].norm()).item():.2e}")
+    print("# worst error / bound of each class (dtype, bf16 fc gradients, tensor, slicing, ratio, error, where)")
+    for (dtype, bf, (t, s)), (r, e, name) in sorted(worst.items()):
+        print(f"worst {dtype} local_bf16={int(bf)} {t} {s} {r:.3f} {e:.3e} [{name}]")
+    print("# worst update ratios (v: 2^-22 relative; p: 2^-24 |p_ref| + 2^-18 |dp_ref|)")
+    for (dtype, k), r in sorted(ratios.items()):
+        print(f"worst {dtype} {k} ratio {r:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", default="0,1,2")
     ap.add_argument("--slices", action="store_true", help="per-slice errors against the fp64 oracle")
+    ap.add_argument("--fused", action="store_true", help="the fused one-GPU Adam step's consumed gradient and update")
     a = ap.parse_args()
     _native.require()
     dev = torch.device("cuda", 0)
     seeds = [int(s) for s in a.seeds.split(",")]
     if a.slices:
         slices(seeds, dev)
+        return
+    if a.fused:
+        fused(dev)
         return
     worst = {}
     for scale, B in CONFIGS:
