@@ -25,6 +25,7 @@
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
 #include "../optim_rules.h"
+#include "../step_log.h"
 #include "../tfd_kernels.h"
 #include "comm.h"
 #include "hip_util.h"
@@ -493,6 +494,54 @@ class MnistEngine : public torch::CustomClassHolder {
     return out;
   }
 
+  // ---- device step log (csrc/step_log.h) ----
+  // A ring of `capacity` per-step records -- {loss, correct, lr, grad_norm, clip_scale, ok, rows} and the
+  // step number t -- written inside the step by one small launch behind the head kernel of every training
+  // (micro-)batch and, with clipping or the guard, one behind the norm / guard finish: the record of
+  // update t (global_step after it) lives in slot (t - 1) % capacity, so a replayed n-step graph leaves
+  // every step's values behind. 0 turns it off (the default: nothing is allocated and the step is launch
+  // for launch what it was). Observation only: no kernel of the step reads the log. evaluate() and
+  // capture_grads do not log. Like phase timing it takes effect for graphs captured afterwards; a call
+  // that changes the capacity allocates a fresh ring (no slot written) and drops the captured graphs.
+  void set_step_log(int64_t capacity) {
+    TORCH_CHECK(capacity >= 0 && capacity <= (1 << 20), "set_step_log: 0 (off) <= capacity <= 2^20, got ", capacity);
+    if (capacity == slog_cap_) return;
+    for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
+    graphs_.clear();
+    slog_cap_ = capacity;
+    if (capacity == 0) {
+      slog_t_ = slog_rec_ = slog_acc_ = at::Tensor();
+      return;
+    }
+    // host tensors copied over: ready when the call returns, whichever stream the first step runs on.
+    // t = 0 marks a slot no step has written (a record's t is >= 1)
+    slog_t_ = at::zeros({capacity}, at::kLong).to(params_.device());
+    slog_rec_ = at::zeros({capacity, kStepLogFields}, at::kFloat).to(params_.device());
+    slog_acc_ = at::zeros({2}, at::kDouble).to(params_.device());
+  }
+  int64_t step_log_capacity() const { return slog_cap_; }
+  // {t int64 [capacity], records fp32 [capacity][8]}, on the device (share storage with the engine)
+  std::vector<at::Tensor> step_log() {
+    TORCH_CHECK(slog_cap_ > 0, "step_log: set_step_log(capacity > 0) first");
+    return {slog_t_, slog_rec_};
+  }
+  // Cost probe: `iters` launches of the loss-mode kernel alone over this engine's rows, timed with HIP
+  // events; returns ms per launch. Rewrites the record of the next update with the same values.
+  double step_log_probe(int64_t iters) {
+    TORCH_CHECK(slog_cap_ > 0 && iters >= 1, "step_log_probe: set_step_log first, iters >= 1");
+    hipStream_t s = stream();
+    const int64_t* c = (const int64_t*)step_.data_ptr();
+    log_loss(c, SL_WHOLE, s, 1);  // warm
+    HipEvent e0(true), e1(true);
+    HIP_OK(hipEventRecord(e0, s));
+    for (int64_t i = 0; i < iters; ++i) log_loss(c, SL_WHOLE, s, 1);
+    HIP_OK(hipEventRecord(e1, s));
+    HIP_OK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    return (double)ms / (double)iters;
+  }
+
   // ---- step pieces (current HIP stream) ----
   void forward(bool train) {
     if (fp32_) mnist_f32_forward(args_f32(), train, stream());
@@ -617,6 +666,7 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("conv_fwd", s);
     mnist_forward_fc(a, true, s);
     tag("fc_fwd", s);
+    log_loss(a.step, SL_WHOLE, s);
     mark(P_FWD, s);
     mnist_backward_a(a, s);
     tag("fc_bwd", s);
@@ -665,6 +715,7 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     mnist_forward_fc(a, true, s);
     tag("fc_fwd", s);
+    log_loss(a.step, SL_WHOLE, s);
     mark(P_FWD, s);
     mnist_backward_a(a, s, 0);
     tag("fc_bwd", s);
@@ -732,6 +783,7 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("fc_fwd", s);
     mark(P_FWD, s);
     hand_off(s, ev_a_, comm_stream_, "gather_dr<-fc_fwd");
+    log_loss(a.step, SL_WHOLE, s);  // behind the hand-off: the factor gather does not wait for it
     gather_sfb(false, comm_stream_);
     tag("gather_dr", comm_stream_);
     mark(P_CA1, comm_stream_);
@@ -821,6 +873,7 @@ class MnistEngine : public torch::CustomClassHolder {
     if (fused) f.t_out = (int64_t*)tnext_.data_ptr();
     mark(P_START, s);
     mnist_f32_forward(f, true, s);
+    log_loss(f.step, SL_WHOLE, s);
     mark(P_FWD, s);
     mnist_f32_backward(f, s);
     mark(P_BFC, s);
@@ -872,6 +925,7 @@ class MnistEngine : public torch::CustomClassHolder {
       MnistF32Args f = args_f32();
       mnist_f32_forward(f, true, s);
       tag("fwd", s);
+      log_loss(f.step, SL_WHOLE, s);
       mark(P_FWD, s);
       mnist_f32_backward(f, s);
       tag("bwd", s);
@@ -891,6 +945,7 @@ class MnistEngine : public torch::CustomClassHolder {
       tag("conv_fwd", s);
       mnist_forward_fc(a, true, s);
       tag("fc_fwd", s);
+      log_loss(a.step, SL_WHOLE, s);
       mark(P_FWD, s);
       mnist_backward_a(a, s, 0);
       tag("fc_bwd", s);
@@ -938,6 +993,8 @@ class MnistEngine : public torch::CustomClassHolder {
       grad_norm_finish(part, grad_norm_blocks(TOTAL), (float)scale, (float)clip_norm_, pair, s);
       tag("grad_norm", s);
     }
+    // after the step bump (both callers): the triple goes into the record of update global_step
+    if (guard_ || clip_norm_ > 0) log_norm(s);
     // the step's clip factor and the guard's ok on the device; null without
     apply_optimizer_range(0, TOTAL, scale, 0, s, nullptr, guard_ || clip_norm_ > 0 ? pair + 1 : nullptr,
                           guard_ ? pair + 2 : nullptr);
@@ -970,6 +1027,7 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_START, s);
     for (int64_t j = 0; j < K; ++j) {
       const bool last = j == K - 1;
+      const int log_mode = last ? SL_EMIT : (j == 0 ? SL_STORE : SL_ADD);
       MnistStepArgs a = args();
       a.step = micro;
       a.step_bump = micro;
@@ -981,6 +1039,7 @@ class MnistEngine : public torch::CustomClassHolder {
         MnistF32Args f = args_f32(a);
         mnist_f32_forward(f, true, s);
         tag("fwd", s);
+        log_loss(micro, log_mode, s);
         if (last) mark(P_FWD, s);
         mnist_f32_backward(f, s);
         tag("bwd", s);
@@ -993,6 +1052,7 @@ class MnistEngine : public torch::CustomClassHolder {
         tag("conv_fwd", s);
         mnist_forward_fc(a, true, s);
         tag("fc_fwd", s);
+        log_loss(micro, log_mode, s);
         if (last) mark(P_FWD, s);
         mnist_backward_a(a, s, 0);
         tag("fc_bwd", s);
@@ -1045,6 +1105,7 @@ class MnistEngine : public torch::CustomClassHolder {
     mnist_forward_conv(a, s);
     wait(s, ev_ag_, "zero:fc_fwd<-wag");
     mnist_forward_fc(a, true, s);
+    log_loss(a.step, SL_WHOLE, s);
     // bf16 wire format for both buckets, produced by the kernels themselves -- the same rounding
     // points as train_step_dp (the conv bucket used to be summed from fp32 and rounded after the
     // sum here, so ZeRO and replicated DP differed by bf16 rounding of the conv gradients)
@@ -1321,6 +1382,40 @@ class MnistEngine : public torch::CustomClassHolder {
     mark(P_CB0, comm_stream_);
     mark(P_CB1, comm_stream_);
     hand_off(comm_stream_, ev_done_, s, out);
+  }
+
+  // ---- device step log: the two launches (no-ops with the log off) ----
+  StepLogArgs log_args(int mode, const int64_t* counter) {
+    StepLogArgs g{};
+    g.t = (int64_t*)slog_t_.data_ptr();
+    g.rec = (float*)slog_rec_.data_ptr();
+    g.capacity = slog_cap_;
+    g.counter = counter;
+    g.mode = mode;
+    return g;
+  }
+  // behind the head kernel on its stream; counter: what the head read (global_step, or the micro
+  // counter under accumulation), not yet bumped. acc_mode: SL_WHOLE, or the micro-batch's store / add / emit
+  void log_loss(const int64_t* counter, int acc_mode, hipStream_t s, int64_t K = 0) {
+    if (!slog_cap_) return;
+    StepLogArgs g = log_args(SL_LOSS, counter);
+    g.acc_mode = acc_mode;
+    g.accum = K ? K : (acc_mode == SL_WHOLE ? 1 : accum_);
+    g.loss_row = (const float*)loss_row_.data_ptr();
+    g.correct_row = (const float*)correct_row_.data_ptr();
+    g.B = (int)B_;
+    g.acc = (double*)slog_acc_.data_ptr();
+    g.sched = sched_;
+    tfd::step_log(g, s);
+    tag("step_log", s);
+  }
+  // behind the norm / guard finish on its stream, after the step bump
+  void log_norm(hipStream_t s) {
+    if (!slog_cap_) return;
+    StepLogArgs g = log_args(SL_NORM, (const int64_t*)step_.data_ptr());
+    g.triple = (const float*)gnorm_.data_ptr();
+    tfd::step_log(g, s);
+    tag("step_log_norm", s);
   }
 
   // ---- argument structs of the optimizer kernels: each is filled in one place ----
@@ -1719,6 +1814,10 @@ class MnistEngine : public torch::CustomClassHolder {
   // accumulator and the device micro-batch counter
   int64_t accum_ = 1;
   at::Tensor acc_, micro_;
+  // device step log (set_step_log): capacity (0 = off), the ring {t, records} and, under accumulation,
+  // the two fp64 sums carried from micro-batch to micro-batch
+  int64_t slog_cap_ = 0;
+  at::Tensor slog_t_, slog_rec_, slog_acc_;
   // moving average of the weights (set_ema): 0 = off; the fp32 shadow, its bf16 image for
   // evaluate(use_ema) (cast when stale); one_: the device 1.0f of OptMods::one
   double ema_decay_ = 0.0;
@@ -1781,6 +1880,10 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("grad_accum", &MnistEngine::grad_accum)
       .def("micro_step_tensor", &MnistEngine::micro_step_tensor)
       .def("sync_micro_step", &MnistEngine::sync_micro_step)
+      .def("set_step_log", &MnistEngine::set_step_log)
+      .def("step_log_capacity", &MnistEngine::step_log_capacity)
+      .def("step_log", &MnistEngine::step_log)
+      .def("step_log_probe", &MnistEngine::step_log_probe)
       .def("set_dataset", &MnistEngine::set_dataset)
       .def("invalidate_prefetch", &MnistEngine::invalidate_prefetch)
       .def("set_debug_buffer", &MnistEngine::set_debug_buffer)

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -21,6 +21,7 @@ import torch  # noqa: E402
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
 from tensorflow_distributed_amd.training import checkpoint  # noqa: E402
+from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
 from tensorflow_distributed_amd.training.optimizers import (AdagradOptimizer, AdamOptimizer, LAMBOptimizer,  # noqa: E402
                                                             LARSOptimizer, RMSPropOptimizer)
 from tensorflow_distributed_amd.utils import input_data  # noqa: E402
@@ -81,6 +82,10 @@ def main(argv=None):
     ap.add_argument("--grad_accum_steps", type=int, default=1, help="gradient accumulation: every optimizer step sums "
                     "this many micro-batches of --batch_size rows (GPU: on the device, inside the step graph); steps "
                     "and Iter count optimizer steps of grad_accum_steps * batch_size images; 1 = off")
+    ap.add_argument("--steps_per_call", type=int, default=1, help="TF's iterations_per_loop: optimizer steps per host "
+                    "round trip. N > 1 replays N steps as one captured graph and reads their losses once per call from "
+                    "the device step log; a call also ends at every --display_step multiple (the minibatch-loss forward "
+                    "needs the last batch). GPU with the device-resident split only; 1 = one step per call")
     ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
                     "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
@@ -88,6 +93,15 @@ def main(argv=None):
         ap.error("--ema_decay must be in (0, 1) (0 = off)")
     if a.grad_accum_steps < 1:
         ap.error("--grad_accum_steps must be >= 1 (1 = off)")
+    if a.steps_per_call < 1 or a.steps_per_call > 1000:
+        ap.error("--steps_per_call must be in [1, 1000] (1 = off)")
+    if a.steps_per_call > 1:
+        if a.cpu or not torch.cuda.is_available():
+            ap.error("--steps_per_call > 1 needs the GPU engine (the CPU path steps from the host)")
+        if a.host_feed:
+            ap.error("--steps_per_call > 1 with --host_feed: a host-fed batch crosses to the device before every step")
+        if a.no_graph:
+            ap.error("--steps_per_call > 1 with --no_graph: the steps of a call are one captured graph")
     step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
@@ -127,6 +141,24 @@ def main(argv=None):
     train_flag = a.train_flag
     step = 1
     if train_flag == 1:
+        if a.steps_per_call > 1:
+            # the same steps, --steps_per_call at a time: one replayed graph, one read of the step log
+            total = max(0, -(-a.training_iters // step_rows) - 1)  # the steps the loop below would take
+            first = runner.global_step()
+            runner.set_step_log(1024)
+            recs = []
+            for k in call_lengths(0, a.steps_per_call, total, multiples(a.display_step, 0, total)):
+                runner.train_steps(k)
+                recs = runner.read_step_log(first + step, first + step + k - 1)
+                step += k
+                if (step - 1) % a.display_step == 0:
+                    batch_x, batch_y = runner.last_device_batch()
+                    loss_sum, _ = runner.evaluate(batch_x, batch_y)
+                    print("Iter " + str((step - 1) * step_rows) + ", Minibatch Loss= " + "{:.6f}".format(loss_sum / len(batch_x)))
+            if recs:
+                print("Last call of %d step(s): training loss %.6f, training accuracy %.4f (dropout on)" % (
+                    len(recs), sum(r["loss"] for r in recs) / len(recs),
+                    sum(r["correct"] for r in recs) / float(sum(r["rows"] for r in recs))))
         # Keep training until reach max iterations
         while step * step_rows < a.training_iters:
             if device_input:

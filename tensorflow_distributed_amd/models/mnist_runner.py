@@ -159,6 +159,18 @@ class MnistRunnerBase:
     def powers(self) -> "dict":
         return {}
 
+    # -- step log: one record per optimizer step (set_step_log / train_steps / read_step_log) --
+    STEP_LOG_KEYS = ("step", "loss", "correct", "rows", "lr", "grad_norm", "clip_scale", "ok")
+
+    @staticmethod
+    def _check_log_range(first_t: int, last_t: int, capacity: int) -> None:
+        if capacity <= 0:
+            raise ValueError("read_step_log: the step log is off; set_step_log() first")
+        if first_t < 1 or last_t < first_t:
+            raise ValueError("read_step_log: need 1 <= first_t <= last_t, got %d..%d" % (first_t, last_t))
+        if last_t - first_t + 1 > capacity:
+            raise ValueError("read_step_log: steps %d..%d are more than the log's capacity %d" % (first_t, last_t, capacity))
+
     def load_flat(self, flat: torch.Tensor, slots: "dict", step: int) -> None: ...
 
 
@@ -179,6 +191,9 @@ class TorchMnistRunner(MnistRunnerBase):
         self._step = 0
         self.gen = torch.Generator(device=self.device).manual_seed(seed * 7919 + rank)
         self.comm = None  # DP reducer: callable(flat_grad) -> None (in-place average)
+        self._log_cap = 0   # step log (set_step_log): capacity, 0 = off
+        self._log = {}      # slot -> record
+        self._log_sums = []  # (loss sum, correct, rows) of the current step's micro-batches
 
     def params(self) -> torch.Tensor:
         return self.flat
@@ -251,6 +266,9 @@ class TorchMnistRunner(MnistRunnerBase):
         self.flat.requires_grad_(False)
         self.grad.copy_(g)
         self._last_loss = float(loss.item())
+        if self._log_cap:  # this micro-batch's share of the step's record
+            self._log_sums.append((self._last_loss * x.shape[0], int((logits.detach().argmax(1) == y.long()).sum().item()),
+                                   int(x.shape[0])))
         return self.grad, self._last_loss
 
     def apply_grads(self, grad: torch.Tensor, scale: float = 1.0) -> None:
@@ -262,11 +280,13 @@ class TorchMnistRunner(MnistRunnerBase):
         own dropout mask drawn in order, are summed in fp32 as the device sums them, reduced once and
         applied once at scale ``1 / accum_steps``. The loss is the last micro-batch's."""
         K, B = self.accum_steps, self.batch_size
+        self._log_sums = []
         if K == 1:
             g, _ = self.compute_grads(x, y)
             if self.comm is not None:
                 self.comm(g)
             self.apply_grads(g)
+            self._log_step()
             return
         x, y = _as_f32(x), _labels_to_ids(y)
         assert x.shape[0] == K * B, f"{x.shape[0]} rows != accum_steps {K} x batch {B}"
@@ -278,6 +298,49 @@ class TorchMnistRunner(MnistRunnerBase):
         if self.comm is not None:
             self.comm(self.grad)
         self.apply_grads(self.grad, 1.0 / K)
+        self._log_step()
+
+    # ---- step log: the device runner's three methods over a plain Python ring ----
+    def set_step_log(self, capacity: int = 1024) -> None:
+        """Keep one record per ``train_step`` -- what the device step log keeps (csrc/step_log.h) -- in a
+        ring of ``capacity`` slots; 0 turns it off."""
+        if capacity < 0:
+            raise ValueError("set_step_log: capacity >= 0 (0 = off)")
+        self._log_cap, self._log, self._log_sums = int(capacity), {}, []
+
+    def _log_step(self) -> None:
+        if not self._log_cap:
+            return
+        t = self._step
+        rows = sum(r for _, _, r in self._log_sums)
+        norm, scale = self.last_grad_norm()
+        self._log[(t - 1) % self._log_cap] = dict(
+            step=t, loss=sum(l for l, _, _ in self._log_sums) / rows, correct=sum(c for _, c, _ in self._log_sums),
+            rows=rows, lr=float(lr_at(self.opt.learning_rate, t - 1)), grad_norm=norm, clip_scale=scale,
+            ok=self.last_step_ok())
+
+    def train_steps(self, n: int, next_batch=None) -> None:
+        """``n`` optimizer steps; ``next_batch()`` -> ``(x, y)`` supplies each step's ``accum_steps *
+        batch_size`` rows (this runner has no device-resident split)."""
+        if next_batch is None:
+            raise ValueError("train_steps: the CPU runner is fed from the host; pass next_batch")
+        if n < 1:
+            raise ValueError("train_steps: n >= 1")
+        for _ in range(n):
+            self.train_step(*next_batch())
+
+    def read_step_log(self, first_t: int, last_t: int) -> list:
+        """The records of steps ``first_t..last_t``; ``ValueError`` when the range exceeds the capacity or a
+        slot holds another step (overwritten or never written)."""
+        self._check_log_range(first_t, last_t, self._log_cap)
+        out = []
+        for t in range(first_t, last_t + 1):
+            rec = self._log.get((t - 1) % self._log_cap)
+            if rec is None or rec["step"] != t:
+                raise ValueError("read_step_log: step %d is not in the log (slot holds %s)"
+                                 % (t, "nothing" if rec is None else "step %d" % rec["step"]))
+            out.append(dict(rec))
+        return out
 
     def last_loss(self) -> float:
         return float(getattr(self, "_last_loss", float("nan")))
@@ -385,6 +448,7 @@ class NativeMnistRunner(MnistRunnerBase):
         self.use_graph = use_graph
         self._graph_ready = False
         self._grads_graph = False
+        self._multi_ready = set()  # lengths n whose n-step graph "train<n>" is captured (train_steps)
         self._x_stage = torch.empty(self.accum_steps * batch_size, 784, dtype=torch.float32).pin_memory()
         self._y_stage = torch.empty(self.accum_steps * batch_size, dtype=torch.int32).pin_memory()
         self.transport = None  # parallel.transport.DPTransport when DP runs over RCCL/IPC
@@ -402,13 +466,60 @@ class NativeMnistRunner(MnistRunnerBase):
 
         self.opt = dataclasses.replace(self.opt, learning_rate=learning_rate)
         self.eng.set_lr_schedule(*schedule_args(learning_rate))
-        self._graph_ready = False
+        self._stale_graphs()
 
     def set_phase_timing(self, on: bool = True) -> None:
         """HIP timing events at the step's phase boundaries (recorded inside the captured graph too).
         Takes effect for graphs captured afterwards."""
         self.eng.set_phase_timing(bool(on))
+        self._stale_graphs()
+
+    def _stale_graphs(self) -> None:
+        """A setting baked into captured step graphs changed: the next step captures again."""
         self._graph_ready = False
+        self._multi_ready.clear()
+
+    # ---- device step log (csrc/step_log.h) ----
+    def set_step_log(self, capacity: int = 1024) -> None:
+        """Keep a device-side ring of ``capacity`` per-step records -- loss, correct, lr and, with
+        ``clip_norm`` / ``skip_nonfinite``, the norm, the clip factor and the guard's decision -- written
+        inside the step graph, so ``train_steps(n)`` needs no host read per step. 0 turns it off. Takes
+        effect for graphs captured afterwards: the captured ones are dropped."""
+        if capacity < 0:
+            raise ValueError("set_step_log: capacity >= 0 (0 = off)")
+        if int(capacity) == int(self.eng.step_log_capacity()):
+            return
+        self.stream.synchronize()  # the engine drops its graphs: none may still be running
+        with torch.cuda.stream(self.stream):
+            self.eng.set_step_log(int(capacity))
+        self._stale_graphs()
+        self._grads_graph = False
+
+    def read_step_log(self, first_t: int, last_t: int) -> list:
+        """The records of optimizer steps ``first_t..last_t`` (``t`` = global_step after the step) as dicts
+        ``{step, loss, correct, rows, lr, grad_norm, clip_scale, ok}``: one synchronisation and one copy.
+        ``ValueError`` when the range exceeds the capacity or a slot holds another step (overwritten, or
+        never written)."""
+        cap = int(self.eng.step_log_capacity())
+        self._check_log_range(first_t, last_t, cap)
+        with torch.cuda.stream(self.stream):
+            t_dev, rec_dev = self.eng.step_log()
+            lo, hi = (first_t - 1) % cap, (last_t - 1) % cap + 1
+            if lo < hi:  # the slots are one run of the ring: views, no gather
+                t_sel, rec_sel = t_dev[lo:hi], rec_dev[lo:hi]
+            else:        # the run wraps
+                t_sel, rec_sel = torch.cat([t_dev[lo:], t_dev[:hi]]), torch.cat([rec_dev[lo:], rec_dev[:hi]])
+            # t's two 32-bit halves ride beside the eight fp32 fields: one device-to-host copy
+            packed = torch.cat([t_sel.view(torch.float32).view(-1, 2), rec_sel], dim=1).cpu()
+        ts = packed[:, :2].contiguous().view(torch.int64).view(-1).tolist()
+        out = []
+        for t, got, r in zip(range(first_t, last_t + 1), ts, packed[:, 2:].tolist()):
+            if got != t:
+                raise ValueError("read_step_log: step %d is not in the log (slot holds %s)"
+                                 % (t, "step %d" % got if got else "nothing"))
+            out.append(dict(step=t, loss=r[0], correct=int(r[1]), rows=int(r[6]), lr=r[2], grad_norm=r[3],
+                            clip_scale=r[4], ok=r[5] != 0.0))
+        return out
 
     def phase_times(self) -> dict:
         """GPU milliseconds of the last step's phases (all 0 when timing is off)."""
@@ -634,6 +745,45 @@ class NativeMnistRunner(MnistRunnerBase):
         if x is not None:
             # the pinned staging buffers are reused next step: wait for the H2D copies to land
             self.stream.synchronize()
+
+    def _steps_to_reshuffle(self) -> int:
+        """Steps until the step boundary where ``_device_batch`` redraws the permutation (>= 1)."""
+        n, rows = self._dev_data.shape[0], self._step_rows
+        return -(-((self._epoch + 1) * n - self._hstep * rows) // rows)
+
+    def train_steps(self, n: int) -> None:
+        """``n`` optimizer steps with no host synchronisation (device input only): one replay of an
+        ``n``-step graph, captured once per distinct ``n``. The permutation is redrawn exactly at the step
+        boundaries where ``train_step(None, None)`` redraws it, so the stream of permutations is the same;
+        a call that such a boundary cuts runs as one-step replays. Read the steps' losses and metrics with
+        ``read_step_log`` (``set_step_log`` first)."""
+        if self._dev_data is None:
+            raise ValueError("train_steps needs the device-resident split (set_device_dataset); host-fed batches "
+                             "go through train_step")
+        if not 1 <= n <= 1000:
+            raise ValueError("train_steps: 1 <= n <= 1000 (one captured graph), got %d" % n)
+        left = n
+        while left > 0:
+            self._device_batch()  # the reshuffle, when one is due at this boundary
+            k = min(left, max(1, self._steps_to_reshuffle()))
+            if k == n and self.use_graph:
+                name = "train%d" % n
+                if n in self._multi_ready:
+                    with torch.cuda.stream(self.stream):
+                        self.eng.replay(name, 1)
+                    self._hstep += n
+                else:
+                    # the first call of this length: one-step replays (the first of which runs eagerly, as
+                    # train_step's does), then the capture for the calls to come
+                    for _ in range(n):
+                        self.train_step(None, None)
+                    with torch.cuda.stream(self.stream):
+                        self.eng.capture_train_steps(name, n)
+                    self._multi_ready.add(n)
+            else:
+                for _ in range(k):
+                    self.train_step(None, None)
+            left -= k
 
     def compute_grads(self, x, y, with_loss: bool = True) -> Tuple[torch.Tensor, Optional[float]]:
         """Forward + backward only (no reduction / optimizer). Bumps the engine's local step. With

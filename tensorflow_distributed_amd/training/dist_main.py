@@ -94,6 +94,13 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "clip, trust ratio, all-reduce and update. --train_steps, global_step/sec, checkpoints and "
                      "--eval_at_steps count optimizer steps. 1 = off. Synchronous all-reduce training of --model "
                      "mnist_cnn only")
+    f.DEFINE_integer("steps_per_call", 1, "TF's iterations_per_loop: optimizer steps per host round trip. N > 1 "
+                     "replays N steps as one captured graph with no host synchronisation between them and reads "
+                     "every step's loss, lr, gradient norm and guard decision once per call from the device step "
+                     "log (csrc/step_log.h); a call also ends at every --eval_at_steps value, "
+                     "--check_consistency_every multiple and at --fault_inject_step. The Supervisor, the summaries "
+                     "and the watchdog see one step per call. 1 = one step per call (the default). GPU "
+                     "--device_input training of --model mnist_cnn, one worker or synchronous all-reduce DP")
     f.DEFINE_boolean("sync_replicas", True, "Use the sync_replicas (synchronized replicas) mode, "
                      "wherein the parameter updates from workers are aggregated before applied to "
                      "avoid stale gradients")
@@ -351,6 +358,34 @@ def check_skip_nonfinite_flags(num_workers: int) -> None:
         raise ValueError("--skip_nonfinite with --dp_schedule=%s: the guard reads the whole aggregated gradient on "
                          "every rank, which the SFB / ZeRO schedules never form; use the all-reduce schedule"
                          % FLAGS.dp_schedule)
+
+
+def check_steps_per_call_flags(num_workers: int) -> None:
+    """--steps_per_call N > 1 takes N optimizer steps per host round trip on the device. What it does not
+    cover is a flag error, raised before any process group is built (every rank sees the same flags)."""
+    n = FLAGS.steps_per_call
+    if n < 1 or n > 1000:
+        raise ValueError("--steps_per_call=%d: must be in [1, 1000] (one captured graph; 1 = off)" % n)
+    if n == 1:
+        return
+    which = "--steps_per_call=%d" % n
+    if not FLAGS.sync_replicas:
+        raise ValueError("%s with --sync_replicas=False: a parameter-server worker exchanges its gradient with the "
+                         "ps tasks after every step" % which)
+    r2a = FLAGS.replicas_to_aggregate
+    if r2a is not None and r2a < num_workers:
+        raise ValueError("%s with backup workers (--replicas_to_aggregate=%d < %d workers): the contributors are "
+                         "chosen on the host after every step" % (which, r2a, num_workers))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the ResNet runner has no device step log" % (which, FLAGS.model))
+    if FLAGS.num_gpus <= 0:
+        raise ValueError("%s with --num_gpus=0: the CPU runner steps from the host; the multi-step graph is the "
+                         "GPU engine's" % which)
+    if not FLAGS.device_input:
+        raise ValueError("%s with --device_input=False: a host-fed batch crosses to the device before every step"
+                         % which)
+    if not FLAGS.use_graph:
+        raise ValueError("%s with --use_graph=False: the N steps of a call are one captured graph" % which)
 
 
 def check_ema_flags(num_workers: int) -> None:
@@ -791,6 +826,7 @@ def main(argv=None) -> int:
     check_rules_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
+    check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -847,6 +883,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     from ..utils.tracing import Watchdog, trace_range
     from .grad_sync import make_grad_sync
     from .optimizers import ExponentialMovingAverage, SyncReplicasOptimizer, ema_decay_at, lr_at
+    from .step_calls import call_lengths, multiples
 
     sync, num_workers, is_chief = roles.sync, cluster.num_workers, FLAGS.task_index == 0
     learning_rate = opt.learning_rate  # a float, or a schedule of global_step
@@ -914,9 +951,96 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
         return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
 
+    def after_step(step: int, local_step: int) -> None:
+        """What follows a step -- or, with --steps_per_call, a call's last step -- on the host."""
+        nonlocal eval_time
+        if FLAGS.check_consistency_every and sync and local_step % FLAGS.check_consistency_every == 0:
+            if zero:
+                runner.sync_state()  # every worker: the fc1 shards -> whole fp32 state
+            _check_consistency(runner, server, num_workers)
+        if zero:
+            # the fp32 fc1 master and its Adam slots are sharded over the workers: the chief's timed
+            # checkpoint needs a gather that every worker joins, at agreed global steps
+            save_now = False
+            if step % max(1, FLAGS.zero_sync_every) == 0:
+                due = torch.tensor([1 if sv.save_due() else 0], dtype=torch.int64)
+                dist.all_reduce(due, op=dist.ReduceOp.MAX, group=server.worker_group)
+                save_now = bool(due.item())
+                if save_now:
+                    runner.sync_state()
+            sv.on_step(step, allow_save=save_now)
+        else:
+            sv.on_step(step)
+        while is_chief and eval_at and step >= eval_at[0]:
+            te = time.time()
+            accs = [correct / float(n) for n, correct in (eval_batch() for _ in range(FLAGS.eval_batches))]
+            acc = 100.0 * sum(accs) / len(accs)
+            eval_time += time.time() - te
+            row = dict(steps=eval_at.pop(0), time=time.time() - time_begin - eval_time, accuracy=round(acc, 2),
+                       lr=lr_at(learning_rate, step))
+            perf_rows.append(row)
+            print("Performance row: %d %.1f %.2f %g" % (row["steps"], row["time"], row["accuracy"], row["lr"]))
+            metrics.log(event="performance", **row)
+        if (FLAGS.fault_inject_step >= 0 and FLAGS.task_index == FLAGS.fault_inject_task and restart_attempt == 0
+                and step >= FLAGS.fault_inject_step):
+            print("Worker %d: fault injection at global step %d" % (FLAGS.task_index, step), flush=True)
+            os._exit(17)
+
     time_begin = _training_begins()
     local_step = 0
     step = runner.global_step()
+    if FLAGS.steps_per_call > 1:
+        # N steps per host round trip: one replayed N-step graph, then one read of the device step log. Every
+        # rank forms the same call lengths from the same flags (the collectives are inside the graphs).
+        assert device_input and not roles.ps_mode and roles.r2a >= num_workers, "--steps_per_call: check_steps_per_call_flags"
+        runner.set_step_log(1024)
+        cuts = list(eval_at) + multiples(FLAGS.check_consistency_every if sync else 0, step, FLAGS.train_steps, origin=step)
+        if FLAGS.fault_inject_step >= 0:
+            cuts.append(FLAGS.fault_inject_step)
+        if zero:  # the workers agree on the chief's checkpoint at these global steps
+            cuts += multiples(max(1, FLAGS.zero_sync_every), step, FLAGS.train_steps)
+        skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
+        for k in call_lengths(step, FLAGS.steps_per_call, FLAGS.train_steps, cuts):
+            t0 = time.time()
+            with timer.phase("step"), trace_range("train_steps"):
+                runner.train_steps(k)
+                recs = runner.read_step_log(step + 1, step + k)  # the call's one synchronisation
+            watchdog.kick()
+            now = time.time()
+            step_s = max(now - t0, 1e-9) / k
+            for i, r in enumerate(recs):
+                last = i == k - 1
+                local_step += 1
+                skipped += 0 if r["ok"] else 1
+                if not FLAGS.quiet:
+                    print("%f: Worker %d: training step %d done (global step: %d)" % (now, FLAGS.task_index, local_step,
+                                                                                      r["step"]))
+                if not metrics.path:
+                    continue
+                rec = dict(step=local_step, global_step=r["step"], step_ms=1e3 * step_s, loss=r["loss"],
+                           images_per_sec=step_rows * (num_workers if sync else 1) / step_s, accum_steps=accum,
+                           steps_in_call=k, train_accuracy=r["correct"] / float(r["rows"]))
+                if gsync.logs_lr:
+                    rec["lr"] = r["lr"]
+                if FLAGS.clip_norm > 0:
+                    rec["grad_norm"], rec["clip_scale"] = r["grad_norm"], r["clip_scale"]
+                if last and FLAGS.optimizer in LAYERWISE_OPTIMIZERS:
+                    rec["trust_ratio"] = {k_: v[2] for k_, v in runner.last_layer_norms().items()}
+                if opt.skip_nonfinite:
+                    rec["skipped_steps"], rec["step_ok"] = skipped, r["ok"]
+                if opt.ema_decay:
+                    rec["ema_decay"] = ema_decay_at(opt.ema_decay, r["step"], opt.ema_num_updates)
+                if last and phase_timing:
+                    ph = runner.phase_times()
+                    rec.update(ph)
+                    timer.add_gpu_phases(now, ph)
+                rec.setdefault("allreduce_ms", 0.0 if (not sync or num_workers == 1) else None)
+                metrics.log(**rec)
+            step += k
+            if opt.skip_nonfinite:
+                assert skipped == runner.skipped_steps(), "step log: %d skipped steps counted from the records, " \
+                    "the device counter says %d" % (skipped, runner.skipped_steps())
+            after_step(step, local_step)
     while step < FLAGS.train_steps:
         with timer.phase("input"):
             if device_input:
@@ -953,37 +1077,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 timer.add_gpu_phases(now, ph)
             rec.setdefault("allreduce_ms", 0.0 if (not sync or num_workers == 1) else None)
             metrics.log(**rec)
-        if FLAGS.check_consistency_every and sync and local_step % FLAGS.check_consistency_every == 0:
-            if zero:
-                runner.sync_state()  # every worker: the fc1 shards -> whole fp32 state
-            _check_consistency(runner, server, num_workers)
-        if zero:
-            # the fp32 fc1 master and its Adam slots are sharded over the workers: the chief's timed
-            # checkpoint needs a gather that every worker joins, at agreed global steps
-            save_now = False
-            if step % max(1, FLAGS.zero_sync_every) == 0:
-                due = torch.tensor([1 if sv.save_due() else 0], dtype=torch.int64)
-                dist.all_reduce(due, op=dist.ReduceOp.MAX, group=server.worker_group)
-                save_now = bool(due.item())
-                if save_now:
-                    runner.sync_state()
-            sv.on_step(step, allow_save=save_now)
-        else:
-            sv.on_step(step)
-        while is_chief and eval_at and step >= eval_at[0]:
-            te = time.time()
-            accs = [correct / float(n) for n, correct in (eval_batch() for _ in range(FLAGS.eval_batches))]
-            acc = 100.0 * sum(accs) / len(accs)
-            eval_time += time.time() - te
-            row = dict(steps=eval_at.pop(0), time=time.time() - time_begin - eval_time, accuracy=round(acc, 2),
-                       lr=lr_at(learning_rate, step))
-            perf_rows.append(row)
-            print("Performance row: %d %.1f %.2f %g" % (row["steps"], row["time"], row["accuracy"], row["lr"]))
-            metrics.log(event="performance", **row)
-        if (FLAGS.fault_inject_step >= 0 and FLAGS.task_index == FLAGS.fault_inject_task and restart_attempt == 0
-                and step >= FLAGS.fault_inject_step):
-            print("Worker %d: fault injection at global step %d" % (FLAGS.task_index, step), flush=True)
-            os._exit(17)
+        after_step(step, local_step)
 
     watchdog.stop()
     if zero:
