@@ -187,6 +187,13 @@ at::Tensor lr_schedule_eval_op(const at::Tensor& steps, std::string kind, std::v
 
 void noop_op(int64_t blocks) { noop_launch((int)blocks, cur()); }
 
+void kernarg_probe_op(const at::Tensor& src, at::Tensor dst, int64_t blocks, bool preload) {
+  TORCH_CHECK(src.is_cuda() && dst.is_cuda() && src.scalar_type() == at::kFloat && dst.scalar_type() == at::kFloat &&
+                  src.is_contiguous() && dst.is_contiguous(), "kernarg_probe: contiguous fp32 GPU tensors");
+  TORCH_CHECK(blocks > 0 && src.numel() >= blocks * 64 && dst.numel() >= blocks * 64, "kernarg_probe: blocks x 64 elements");
+  kernarg_probe((const float*)src.data_ptr(), (float*)dst.data_ptr(), (int)blocks, preload, cur());
+}
+
 at::Tensor to_bf16(const at::Tensor& x) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat, "to_bf16: fp32 GPU");
   auto xc = x.contiguous();
@@ -232,6 +239,8 @@ TORCH_LIBRARY(tfd, m) {
   m.impl("lr_schedule_eval", c10::DispatchKey::CUDA, &lr_schedule_eval_op);
   m.def("noop(int blocks) -> ()");
   m.impl("noop", c10::DispatchKey::CompositeExplicitAutograd, &noop_op);
+  m.def("kernarg_probe(Tensor src, Tensor(a!) dst, int blocks, bool preload) -> ()");
+  m.impl("kernarg_probe", c10::DispatchKey::CUDA, &kernarg_probe_op);
   m.def("to_bf16(Tensor x) -> Tensor");
   m.impl("to_bf16", c10::DispatchKey::CUDA, &to_bf16);
 }

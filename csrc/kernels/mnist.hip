@@ -181,7 +181,26 @@ static_assert(C12_IOFF % 16 == 0, "LDS carve alignment");
   do {                                                                                     \
     if (TFD_STAMP && a.dbg && threadIdx.x == 256) a.dbg[blockIdx.x * 16 + 8 + (k)] = (int64_t)__builtin_amdgcn_s_memtime(); \
   } while (0)
-__global__ __launch_bounds__(512) void conv12_fwd_lds(MnistStepArgs a) {
+// Leading parameters (here and in every kernel of the step): the pointers and B that the first load
+// batch needs, in order of first use, passed directly so that they are preloaded into SGPRs at wave
+// launch (this file is compiled with kernel-argument preload; a by-value struct never is). Each kernel
+// has ONE list of its hot fields of MnistStepArgs (X_HOT); the parameters (HOT_PARAM: each with its field's
+// type), the overlay (HOT_SET) and the launch's arguments (HOT_PASS: the struct's own values) are all
+// expanded from it, so a launch cannot hand a kernel anything but a.f for its f. HOT_SET puts the
+// parameters over the struct's fields: the body reads `a` as before and the compiler takes the hot fields
+// from the preloaded registers; every other field is still a scalar load of the argument segment.
+// docs/DESIGN.md section 8c.
+#define HOT_PARAM(f) decltype(MnistStepArgs::f) f,
+#define HOT_SET(f) a.f = f;
+#define HOT_PASS(f) a.f,
+#define CONV12_HOT(X) X(pbf) X(p32) X(xpre) X(rows) X(step) X(perm) X(B)
+#define FC1F_HOT(X) X(p2) X(pbf) X(fc1_slab) X(B)
+#define HEAD_HOT(X) X(fc1_slab) X(p32) X(step) X(rows) X(ypre) X(perm) X(B)
+#define FC1B_HOT(X) X(dh) X(pbf) X(p2) X(idx2) X(dz2) X(B)
+#define C2B_HOT(X) X(dz2) X(pbf) X(perm) X(step) X(rows) X(p1) X(B)
+__global__ __launch_bounds__(512) void conv12_fwd_lds(CONV12_HOT(HOT_PARAM) MnistStepArgs a_) {
+  MnistStepArgs a = a_;
+  CONV12_HOT(HOT_SET)
   C12_STAMP(0);
   C12_STAMPW(0);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -418,7 +437,9 @@ constexpr int FC1_BM = 64, FC1_BN = 64, FC1_BK = FC1_BK_;
 constexpr int FC1_SPLITS = 7;  // 3136 = 7 * 448; each split's whole K range in one round trip (14: +0.5 us)
 constexpr int FC1_NKT = FEAT / FC1_SPLITS / FC1_BK;  // K-tiles per split
 static_assert(FC1_NKT * FC1_BK * FC1_SPLITS == FEAT, "fc1 split-K must tile K exactly");
-__global__ __launch_bounds__(256) void fc1_fwd(MnistStepArgs a, int kper) {
+__global__ __launch_bounds__(256) void fc1_fwd(FC1F_HOT(HOT_PARAM) int kper, MnistStepArgs a_) {
+  MnistStepArgs a = a_;
+  FC1F_HOT(HOT_SET)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(FEAT % 8 == 0 && HID % 8 == 0, "whole chunks (DenseLoaderX)");
   DenseLoaderX<true> la{a.p2, FEAT, a.B, FEAT};
@@ -435,7 +456,9 @@ __global__ __launch_bounds__(256) void fc1_fwd(MnistStepArgs a, int kper) {
   do {                                                                                                   \
     if (TFD_STAMP && a.dbg && threadIdx.x == 0) a.dbg[4 * a.B * 8 + blockIdx.x * 8 + (k)] = (int64_t)__builtin_amdgcn_s_memtime(); \
   } while (0)
-__global__ __launch_bounds__(256) void head_kernel(MnistStepArgs a, int train) {
+__global__ __launch_bounds__(256) void head_kernel(HEAD_HOT(HOT_PARAM) MnistStepArgs a_, int train) {
+  MnistStepArgs a = a_;
+  HEAD_HOT(HOT_SET)
   HEAD_STAMP(0);
   const int row = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int n0 = 4 * t;
@@ -822,7 +845,9 @@ __device__ __forceinline__ void fdx_tile(int j, int gx, int gy, int& bx, int& by
   bx = T / gy;
   by = T - bx * gy;
 }
-__global__ __launch_bounds__(256) void fc1_bwd(MnistStepArgs a, int n_dx, int part) {
+__global__ __launch_bounds__(256) void fc1_bwd(FC1B_HOT(HOT_PARAM) int n_dx, int part, MnistStepArgs a_) {
+  MnistStepArgs a = a_;
+  FC1B_HOT(HOT_SET)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   int id = blockIdx.x;
   const int gy = (a.B + FDX_BM - 1) / FDX_BM;
@@ -832,22 +857,24 @@ __global__ __launch_bounds__(256) void fc1_bwd(MnistStepArgs a, int n_dx, int pa
     fc1_dx_block<FDX_BN2, FDX_RS_ALONE>(a, bx, by, (bf16*)smem_raw);
     return;
   }
-  // the 17 output-layer blocks each walk the whole batch: dispatched first, their latency hides
-  // under the GEMM tiles instead of forming the kernel's tail.
+  // Block ids: [the 17 output-layer blocks | part 0: the dX blocks | the dW blocks]. The output-layer
+  // blocks each walk the whole batch: dispatched first, their latency hides under the GEMM tiles
+  // instead of forming the kernel's tail. The dX blocks (K = 1024: 16 k-steps each) get the next ids
+  // so they are dispatched before the short dW blocks (K = B), which fill in around them, instead
+  // of the long blocks starting last and forming the kernel's tail.
+  // The dX role is tested for FIRST: every pointer it reads is a leading parameter, and the other
+  // roles' scalar loads of the argument segment (dlogits, hd, grad, gbf_a) are then requested behind
+  // this branch. In front of it they were outstanding when the dX blocks issued their first DMA
+  // stage, which waited for them.
+  if (part == 0 && id >= OUTG_BLOCKS && id - OUTG_BLOCKS < n_dx) {
+    int bx, by;
+    fdx_tile(id - OUTG_BLOCKS, FDX_GX, gy, bx, by);
+    fc1_dx_block_dma(a, bx, by, smem_raw);
+    return;
+  }
   if (id < OUTG_BLOCKS) { out_grad_block(a, id, (float*)smem_raw); return; }
   id -= OUTG_BLOCKS;
-  // part 0: the dX blocks (K = 1024: 16 k-steps each) get the lowest block ids so they are
-  // dispatched first and the short dW blocks (K = B) fill in around them, instead of the long
-  // blocks starting last and forming the kernel's tail.
-  if (part == 0) {
-    if (id < n_dx) {
-      int bx, by;
-      fdx_tile(id, FDX_GX, gy, bx, by);
-      fc1_dx_block_dma(a, bx, by, smem_raw);
-      return;
-    }
-    id -= n_dx;
-  }
+  if (part == 0) id -= n_dx;
   if (id < FDW_GX * FDW_GY) fc1_dw_block(a, id % FDW_GX, id / FDW_GX, (bf16*)smem_raw);
 }
 
@@ -1356,7 +1383,9 @@ __device__ __forceinline__ void conv2_wgrad_body(const MnistStepArgs& a, const i
 // conv2 wgrad and dgrad (+ the conv1 wgrad tail) in ONE launch: both consume only dz2. Blocks [0, nw)
 // wgrad, then dgrad; 4-wave blocks at <= 68 KB of LDS, two per CU, all resident at once, so one block's
 // operand waits overlap the other's MFMA / LDS phases (8-wave 131-KB blocks ran in two serial waves).
-__global__ __launch_bounds__(C2B_NT, 2) void conv2_bwd_lds(MnistStepArgs a, int nw) {
+__global__ __launch_bounds__(C2B_NT, 2) void conv2_bwd_lds(C2B_HOT(HOT_PARAM) int nw, MnistStepArgs a_) {
+  MnistStepArgs a = a_;
+  C2B_HOT(HOT_SET)
   if ((int)blockIdx.x < nw) {
     conv2_wgrad_body(a, blockIdx.x);
   } else {
@@ -1468,7 +1497,7 @@ void mnist_forward(const MnistStepArgs& a, bool train, hipStream_t s) {
 
 void mnist_forward_conv(const MnistStepArgs& a, hipStream_t s) {
   set_smem<conv12_fwd_lds>(C12_SMEM);
-  TFD_LAUNCH(conv12_fwd_lds<<<2 * a.B, 512, C12_SMEM, s>>>(a));
+  TFD_LAUNCH(conv12_fwd_lds<<<2 * a.B, 512, C12_SMEM, s>>>(CONV12_HOT(HOT_PASS) a));
 }
 
 void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
@@ -1479,9 +1508,9 @@ void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
     set_smem<fc1_fwd>(sm);
     const int kper = (FEAT + a.fc1_splits - 1) / a.fc1_splits;
     dim3 g(HID / FC1_BN, (B + FC1_BM - 1) / FC1_BM, a.fc1_splits);
-    TFD_LAUNCH(fc1_fwd<<<g, 256, sm, s>>>(a, kper));
+    TFD_LAUNCH(fc1_fwd<<<g, 256, sm, s>>>(FC1F_HOT(HOT_PASS) kper, a));
   }
-  TFD_LAUNCH(head_kernel<<<B, 256, 0, s>>>(a, train ? 1 : 0));
+  TFD_LAUNCH(head_kernel<<<B, 256, 0, s>>>(HEAD_HOT(HOT_PASS) a, train ? 1 : 0));
 }
 
 void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {
@@ -1495,7 +1524,7 @@ void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {
   set_smem<fc1_bwd>(sm);
   const int n_dx = FDX_GX * ((B + FDX_BM - 1) / FDX_BM);
   const int nb = part == 2 ? FDX_GX2 * ((B + FDX_BM - 1) / FDX_BM) : FDW_GX * FDW_GY + (part == 0 ? n_dx : 0) + OUTG_BLOCKS;
-  TFD_LAUNCH(fc1_bwd<<<nb, 256, sm, s>>>(a, n_dx, part));
+  TFD_LAUNCH(fc1_bwd<<<nb, 256, sm, s>>>(FC1B_HOT(HOT_PASS) n_dx, part, a));
 }
 
 void mnist_backward_b(const MnistStepArgs& a, hipStream_t s) {
@@ -1504,7 +1533,7 @@ void mnist_backward_b(const MnistStepArgs& a, hipStream_t s) {
   static_assert(C2WL_SMEM <= C2D_SMEM, "conv2_bwd_lds: the dgrad LDS size covers the wgrad blocks");
   set_smem<conv2_bwd_lds>(C2D_SMEM);
   const int nw = C2WL_NTG * a.wg2_splits;
-  TFD_LAUNCH(conv2_bwd_lds<<<nw + 2 * a.B, C2B_NT, C2D_SMEM, s>>>(a, nw));
+  TFD_LAUNCH(conv2_bwd_lds<<<nw + 2 * a.B, C2B_NT, C2D_SMEM, s>>>(C2B_HOT(HOT_PASS) nw, a));
 }
 
 void mnist_conv_grad_reduce(const MnistStepArgs& a, hipStream_t s) {

@@ -38,7 +38,8 @@ __device__ __forceinline__ void gather_next(const MnistStepArgs& a, int64_t next
     if (b == 0) a.rows[a.B] = (int)next;
   }
 }
-__device__ __forceinline__ int gather_blocks(const MnistStepArgs& a) { return (a.perm && a.xpre) ? a.B : 0; }
+// (counted by the launcher: the tail takes the number as a leading kernel parameter)
+inline int gather_blocks(const MnistStepArgs& a) { return (a.perm && a.xpre) ? a.B : 0; }
 
 // ---------------- one-GPU optimizer tail: K16 ApplyAdam with the K12/K14/K15 slab reduce fused ----------------
 // Grid = [13 conv1 blocks | 201 conv2 blocks | MAD_FC_BLOCKS grid-stride blocks]:
@@ -115,27 +116,45 @@ __device__ __forceinline__ f32x4 slab_sum(const f32x4* __restrict__ s4, int64_t 
 template <class EO> struct TailRates { float lr_t; EO omd; };
 // Opt: MnistAdamConst, MnistAdamArgs or MnistAdamEmaArgs (o: the struct itself or the one the wrapper
 // holds; em: the wrapper's shadow, else an empty tag)
-template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel(MnistStepArgs a, Opt oo, int fcb4) {
+// Leading parameters: what an fc-region block (1024 of the grid's ~1240) needs for its first loads --
+// p / m / v, the bf16 gradient pointer its loop is chosen by (the default step's loop reads it), t's
+// pointer, and the three ints of its first index (gb: the gather blocks in front, the launcher's count;
+// nblk: the grid, read from the hidden arguments behind the structs when taken from gridDim) -- preloaded
+// into SGPRs at wave launch by the kernel-argument preload these files are built with (docs/DESIGN.md
+// section 8c). 13 dwords: the fp32 gradient's pointer has no room among them, so the fp32-gradient loop
+// requests p / m / v and t first and fetches a.grad beside them. mnist_adam_launch alone forms these
+// arguments, from the structs' own values (p0 = o.p, m0 = o.m, v0 = o.v, gbf0 = o.gbf, t0 = o.t); the
+// fc-region loops address their loads through them, everything behind the first loads reads the structs as before. (The
+// structs are not copied with the fields overwritten, as mnist.hip's kernels do with MnistStepArgs: a
+// copy of the scheduled variant's LrSchedule, indexed at run time, would live in scratch.)
+template <class Opt>
+__global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel(const float* p0, const float* m0, const float* v0,
+                                                            const uint16_t* gbf0, const int64_t* t0, int gb,
+                                                            int nblk, int fcb4, MnistStepArgs a, Opt oo) {
   const auto& o = tail_args(oo);
   const auto em = ema_of(oo);
-  const int gb = gather_blocks(a);
   if ((int)blockIdx.x < gb) {  // the next step's batch; t = the step started next
-    gather_next(a, *o.t, blockIdx.x);
+    gather_next(a, *t0, blockIdx.x);
     return;
   }
-  const int grid = (int)gridDim.x - gb;
+  const int grid = nblk - gb;
   // grid == MAD_CONV: the conv region only; the last conv2 block bumps the step
   if (grid == MAD_CONV && (int)blockIdx.x - gb == grid - 1 && threadIdx.x == 0) *o.step += 1;
   // t (a dependent load of the head's step counter) is awaited only where the update needs it,
   // after this thread's first operand loads are out (the optimizer's first memory round trip)
-  auto lr_of = [&]() __attribute__((always_inline)) {  // (a call would wait for every load in flight)
-    const int64_t t = *o.t;
+  auto lr_of = [&](const int64_t t) __attribute__((always_inline)) {  // (a call would wait for every load in flight)
     const float b1p = powf(o.beta1, (float)t), b2p = powf(o.beta2, (float)t);
     return TailRates<decltype(ema_omd(em, t))>{base_lr(o, t) * sqrtf(1.f - b2p) / (1.f - b1p), ema_omd(em, t)};
   };
-  const float c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
+  // (c1 / c2 are formed in each branch behind its first loads: at the top, their scalar loads of the
+  //  argument segment were awaited in front of every block's first vector load)
   const int bid = (int)blockIdx.x - gb, tid = threadIdx.x;
   if (bid < MAD_CONV) {
+    // what either conv region's slab loads take from the argument segment, requested together and awaited
+    // once (the compiler had sunk conv2's pair behind conv1's wait). t stays behind the reduction, read
+    // through its preloaded pointer: requested in front of the slab loads, a uniform load is moved to SGPRs
+    // at once, which awaits it before the first slab address
+    asm volatile("" ::"s"(a.wg1_slab), "s"(a.wg2_slab), "s"(a.B), "s"(a.wg2_splits));
     __shared__ f32x4 red[MAD_NT];
     const bool one = bid < MAD_C1BLK;
     const int q = one ? tid >> 4 : tid >> 6, x = one ? tid & 15 : tid & 63;
@@ -152,7 +171,8 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
       const int nq = one ? 16 : 4, qs = one ? 16 : 64;
       f32x4 s = red[x];
       for (int k = 1; k < nq; ++k) s += red[k * qs + x];
-      const auto r = lr_of();
+      const auto r = lr_of(*t0);
+      const float c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
       adam4(o, i, s, r.lr_t, c1, c2, em, r.omd);
     }
   } else {
@@ -161,11 +181,39 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
     // ADAM_U strides' loads issued before any math/store, so U x 56 B per lane are in flight
     // (the one-at-a-time loop leaves the compiler no room: p/m/v stores may alias the next loads;
     // streaming non-temporal loads/stores were +0.9 us: the next step re-reads p/m/v from MALL)
-    if (o.gbf) {
+    if (gbf0) {
       constexpr int U = ADAM_U;
-      const auto r = lr_of();
-      const float lr_t = r.lr_t;
-      for (int64_t base = i0; base < TOTAL / 4; base += STRIDE * U) {
+      // the first item's p / gbf / m / v and t itself are requested side by side through the preloaded
+      // pointers; t is awaited behind them, where the update needs it
+      uint2 hf = {};
+      f32x4 pf = {}, mf = {}, vf = {};
+      decltype(ema_load4(em, 0)) e0{};
+      if (i0 < TOTAL / 4) {
+        pf = reinterpret_cast<const f32x4*>(p0)[i0];
+        hf = reinterpret_cast<const uint2*>(gbf0)[i0];
+        mf = reinterpret_cast<const f32x4*>(m0)[i0];
+        vf = reinterpret_cast<const f32x4*>(v0)[i0];
+      }
+      const int64_t t = *t0;
+      if (i0 < TOTAL / 4) e0 = ema_load4(em, i0);
+      const auto r = lr_of(t);
+      const float lr_t = r.lr_t, c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
+      auto upd = [&](const int64_t i, f32x4 p, const uint2 h, f32x4 m, f32x4 v, const decltype(e0)& e)
+                     __attribute__((always_inline)) {
+        const f32x4 g = f32x4{__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xFFFF0000u),
+                              __uint_as_float(h.y << 16), __uint_as_float(h.y & 0xFFFF0000u)};
+        m = m + (g - m) * c1;
+        v = v + (g * g - v) * c2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] -= lr_t * m[j] / (sqrtf(v[j]) + o.eps);
+        reinterpret_cast<f32x4*>(o.p)[i] = p;
+        reinterpret_cast<f32x4*>(o.m)[i] = m;
+        reinterpret_cast<f32x4*>(o.v)[i] = v;
+        reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[0], p[1]), pack_bf2(p[2], p[3]));
+        ema_store4(em, i, e, r.omd, p);
+      };
+      if (i0 < TOTAL / 4) upd(i0, pf, hf, mf, vf, e0);
+      for (int64_t base = i0 + STRIDE; base < TOTAL / 4; base += STRIDE * U) {
         uint2 h[U];
         f32x4 p[U], m[U], v[U];
         decltype(ema_load4(em, 0)) e[U];
@@ -173,47 +221,41 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
         for (int u = 0; u < U; ++u) {
           const int64_t i = base + (int64_t)u * STRIDE;
           if (i < TOTAL / 4) {
-            p[u] = reinterpret_cast<const f32x4*>(o.p)[i];
-            h[u] = reinterpret_cast<const uint2*>(o.gbf)[i];
-            m[u] = reinterpret_cast<const f32x4*>(o.m)[i];
-            v[u] = reinterpret_cast<const f32x4*>(o.v)[i];
+            p[u] = reinterpret_cast<const f32x4*>(p0)[i];
+            h[u] = reinterpret_cast<const uint2*>(gbf0)[i];
+            m[u] = reinterpret_cast<const f32x4*>(m0)[i];
+            v[u] = reinterpret_cast<const f32x4*>(v0)[i];
             e[u] = ema_load4(em, i);
           }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int64_t i = base + (int64_t)u * STRIDE;
-          if (i < TOTAL / 4) {
-            const f32x4 g = f32x4{__uint_as_float(h[u].x << 16), __uint_as_float(h[u].x & 0xFFFF0000u),
-                                  __uint_as_float(h[u].y << 16), __uint_as_float(h[u].y & 0xFFFF0000u)};
-            m[u] = m[u] + (g - m[u]) * c1;
-            v[u] = v[u] + (g * g - v[u]) * c2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[u][j] -= lr_t * m[u][j] / (sqrtf(v[u][j]) + o.eps);
-            reinterpret_cast<f32x4*>(o.p)[i] = p[u];
-            reinterpret_cast<f32x4*>(o.m)[i] = m[u];
-            reinterpret_cast<f32x4*>(o.v)[i] = v[u];
-            reinterpret_cast<uint2*>(o.pbf)[i] = make_uint2(pack_bf2(p[u][0], p[u][1]), pack_bf2(p[u][2], p[u][3]));
-            ema_store4(em, i, e[u], r.omd, p[u]);
-          }
+          if (i < TOTAL / 4) upd(i, p[u], h[u], m[u], v[u], e[u]);
         }
       }
     } else {
-      // the first item's p / m / v / g are loaded before t is awaited
-      f32x4 p0 = {}, m0 = {}, v0 = {}, g0 = {};
+      // the first item's p / m / v and t are requested before anything is awaited; the gradient's and the
+      // shadow's pointers are scalar loads of the argument segment, requested side by side behind them and
+      // awaited once
+      const float* const g0 = a.grad;
+      f32x4 pf = {}, mf = {}, vf = {}, gf = {};
       decltype(ema_load4(em, 0)) e0{};
       if (i0 < TOTAL / 4) {
-        e0 = ema_load4(em, i0);
-        p0 = reinterpret_cast<const f32x4*>(o.p)[i0];
-        m0 = reinterpret_cast<const f32x4*>(o.m)[i0];
-        v0 = reinterpret_cast<const f32x4*>(o.v)[i0];
-        g0 = reinterpret_cast<const f32x4*>(a.grad)[i0];
+        pf = reinterpret_cast<const f32x4*>(p0)[i0];
+        mf = reinterpret_cast<const f32x4*>(m0)[i0];
+        vf = reinterpret_cast<const f32x4*>(v0)[i0];
       }
-      const auto r = lr_of();
-      const float lr_t = r.lr_t;
-      if (i0 < TOTAL / 4) adam4_pre(o, i0, p0, m0, v0, g0, lr_t, c1, c2, em, e0, r.omd);
+      const int64_t t = *t0;
+      if (i0 < TOTAL / 4) {
+        gf = reinterpret_cast<const f32x4*>(g0)[i0];
+        e0 = ema_load4(em, i0);
+      }
+      const auto r = lr_of(t);
+      const float lr_t = r.lr_t, c1 = 1.f - o.beta1, c2 = 1.f - o.beta2;
+      if (i0 < TOTAL / 4) adam4_pre(o, i0, pf, mf, vf, gf, lr_t, c1, c2, em, e0, r.omd);
       for (int64_t i = i0 + STRIDE; i < TOTAL / 4; i += STRIDE)
-        adam4(o, i, reinterpret_cast<const f32x4*>(a.grad)[i], lr_t, c1, c2, em, r.omd);
+        adam4(o, i, reinterpret_cast<const f32x4*>(g0)[i], lr_t, c1, c2, em, r.omd);
     }
     if (bid == grid - 1 && tid == 0) *o.step += 1;  // see MnistAdamArgs
   }
@@ -221,8 +263,10 @@ template <class Opt> __global__ __launch_bounds__(MAD_NT) void mnist_adam_kernel
 
 template <class Opt>
 inline void mnist_adam_launch(const MnistStepArgs& a, const Opt& o, hipStream_t s, bool fc_region) {
-  const int gb = (a.perm && a.xpre) ? a.B : 0;
-  TFD_LAUNCH(mnist_adam_kernel<<<gb + MAD_CONV + (fc_region ? MAD_FC_BLOCKS : 0), MAD_NT, 0, s>>>(a, o, (int)(OFF_WD1 / 4)));
+  const int gb = gather_blocks(a);
+  const int nblk = gb + MAD_CONV + (fc_region ? MAD_FC_BLOCKS : 0);
+  const auto& oa = tail_args(o);
+  TFD_LAUNCH(mnist_adam_kernel<<<nblk, MAD_NT, 0, s>>>(oa.p, oa.m, oa.v, oa.gbf, oa.t, gb, nblk, (int)(OFF_WD1 / 4), a, o));
 }
 
 }  // namespace

@@ -102,9 +102,10 @@ __device__ __forceinline__ const SgdArgs& optim_args(const SgdEmaArgs& k) { retu
 __device__ __forceinline__ float clip_load(const AdamEmaArgs& k) { return *k.k.gscale; }
 __device__ __forceinline__ float clip_load(const SgdEmaArgs& k) { return *k.k.gscale; }
 // the fused MNIST tail's view of its argument: the struct itself, or the one the EMA wrapper holds
+// (host too: the launcher passes the view's pointers as the kernel's leading parameters)
 template <class O>
-__device__ __forceinline__ const O& tail_args(const O& o) { return o; }
-__device__ __forceinline__ const MnistAdamArgs& tail_args(const MnistAdamEmaArgs& k) { return k.o; }
+__host__ __device__ __forceinline__ const O& tail_args(const O& o) { return o; }
+__host__ __device__ __forceinline__ const MnistAdamArgs& tail_args(const MnistAdamEmaArgs& k) { return k.o; }
 
 // The non-finite guard (GuardArgs<K>, tfd_kernels.h; optim_guard.hip holds the instantiations): every
 // view above is that of the wrapped K. guard_load is ok of grad_guard.hip's {norm, scale, ok}, read from

@@ -225,6 +225,9 @@ void sgd_apply_guard(const SgdEmaGuardArgs& a, hipStream_t s);
 void stream_floor(float* p, float* m, float* v, const uint16_t* g, uint16_t* pbf, const float* x, int64_t n4, int64_t nx4,
                   int blocks, int unroll, hipStream_t s);
 void noop_launch(int blocks, hipStream_t s);
+// first-argument-fetch probe (kernarg_probe.hip, tools/debug/kernarg_probe.py): dst[i] = src[i] + 1 over
+// blocks x 64 floats, the pointers taken from a 320-byte by-value struct or as preloaded leading parameters
+void kernarg_probe(const float* src, float* dst, int blocks, bool preload, hipStream_t s);
 void sgd_apply(const SgdArgs& a, hipStream_t s);
 // debug probe: out[i] = lr_at(sc, steps[i]) through the device function (one block)
 void lr_schedule_eval(const LrSchedule& sc, const int64_t* steps, float* out, int64_t n, hipStream_t s);

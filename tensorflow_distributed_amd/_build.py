@@ -31,6 +31,12 @@ BUILD = os.path.join(ROOT, "build", "native" + (f"-{VARIANT}" if VARIANT else ""
 OUT = os.path.join(PKG, f"_C_{VARIANT}.so" if VARIANT else "_C.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("TFD_OFFLOAD_ARCH", "gfx950")
+# Kernel-argument preload (docs/DESIGN.md section 8c): in these files the kernels' leading pointer / scalar
+# parameters are placed in SGPRs at wave launch, so the first vector load needs no scalar load of the
+# argument segment in front of it. Per file: every other code object stays byte for byte what it was.
+# tools/isa_waits.py mirrors the flags and the list.
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+PRELOAD_SOURCES = ("mnist.hip", "mnist_tail_sched.hip", "mnist_tail_ema.hip", "kernarg_probe.hip")
 
 
 def _torch_dirs():
@@ -83,7 +89,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     ] + sum([["-I", i] for i in incs], []) + ["-Wno-deprecated-declarations"]
     # a flag change (build options, torch headers) invalidates every object of this variant
     stamp = os.path.join(BUILD, "flags.stamp")
-    sig = repr((hip_flags, cpp_flags))
+    sig = repr((hip_flags, cpp_flags, PRELOAD_FLAGS, PRELOAD_SOURCES))
     if not os.path.exists(stamp) or open(stamp).read() != sig:
         force = True
     jobs_list = []
@@ -92,7 +98,8 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
         o = os.path.join(BUILD, os.path.basename(s) + ".o")
         objs.append(o)
         if force or _needs(s, o, hdr_mtime):
-            jobs_list.append(([os.path.join(ROCM, "bin", "hipcc")] + hip_flags + ["-c", s, "-o", o], s))
+            pre = PRELOAD_FLAGS if os.path.basename(s) in PRELOAD_SOURCES else []
+            jobs_list.append(([os.path.join(ROCM, "bin", "hipcc")] + hip_flags + pre + ["-c", s, "-o", o], s))
     for s in cpp_srcs:
         o = os.path.join(BUILD, os.path.basename(s) + ".o")
         objs.append(o)
