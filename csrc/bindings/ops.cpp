@@ -11,28 +11,117 @@ namespace tfd {
 uint32_t crc32c_extend(uint32_t init, const void* data, size_t n);
 
 namespace {
-using namespace flat_op;  // cur, flat_schedule, ema_shadow, flat_mods
+using namespace flat_op;  // cur, flat_schedule, step_ptr, on_device_of, ema_shadow, flat_mods
 
 int64_t crc32c_op(const at::Tensor& bytes, int64_t init) {
   TORCH_CHECK(!bytes.is_cuda() && bytes.is_contiguous(), "crc32c: contiguous CPU tensor");
   return (int64_t)crc32c_extend((uint32_t)init, bytes.data_ptr(), (size_t)bytes.nbytes());
 }
 
-// Adam's t = *step + t_offset; the schedule is evaluated on the device at s = t - 1
+// The buffers of the flat Adam / Momentum ops, checked as rule_args checks them (rules_ops.cpp): every buffer is
+// contiguous, of p's size and on p's device, the slots fp32, g fp32 or bf16, pbf bf16. An out-of-bounds store of
+// an optimizer is the worst kind there is, so nothing reaches a launcher unchecked.
+void check_params(const at::Tensor& p, const char* who) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous() && p.numel() >= 1, who,
+              ": p is a contiguous fp32 GPU tensor of at least one element");
+}
+float* slot_ptr(const at::Tensor& s, const at::Tensor& p, const char* who, const char* name) {
+  TORCH_CHECK(on_device_of(s, p) && s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() == p.numel(), who, ": ",
+              name, " is a contiguous fp32 tensor of p's size on p's device");
+  return (float*)s.data_ptr();
+}
+// g as {fp32 pointer, bf16 pointer}: exactly one is set
+struct GradPtr { const float* f; const uint16_t* b; };
+GradPtr grad_ptr(const at::Tensor& g, const at::Tensor& p, const char* who) {
+  const bool gb = g.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(on_device_of(g, p) && (gb || g.scalar_type() == at::kFloat) && g.is_contiguous() && g.numel() == p.numel(), who,
+              ": g is a contiguous fp32 or bf16 tensor of p's size on p's device");
+  return GradPtr{gb ? nullptr : (const float*)g.data_ptr(), gb ? (const uint16_t*)g.data_ptr() : nullptr};
+}
+uint16_t* shadow_ptr(const c10::optional<at::Tensor>& pbf, const at::Tensor& p, const char* who) {
+  TORCH_CHECK(!pbf || (on_device_of(*pbf, p) && pbf->scalar_type() == at::kBFloat16 && pbf->is_contiguous() &&
+                       pbf->numel() == p.numel()),
+              who, ": pbf is a contiguous bf16 tensor of p's size on p's device");
+  return pbf ? (uint16_t*)pbf->data_ptr() : nullptr;
+}
+// Adam's kernels read float4 of the fp32 buffers and uint2 of the bf16 ones
+void check_aligned(const void* ptr, size_t bytes, const char* who, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ptr) % bytes == 0, who, ": ", name, " is not ", bytes,
+              "-byte aligned (the kernel reads it as ", bytes == 16 ? "float4" : "uint2", ")");
+}
+// the launchers' own checks (ranges, the guard of the ranges form) as torch errors
+template <class F>
+void launch(F&& f) {
+  try {
+    f();
+  } catch (const std::runtime_error& e) {
+    TORCH_CHECK(false, e.what());
+  }
+}
+
+// what adam_flat and adam_ranges_flat share: every check both make, the kernel's arguments and the modifiers
+struct AdamCall { AdamArgs a; OptMods m; };
+AdamCall adam_flat_args(const char* who, at::Tensor& p, const at::Tensor& m, const at::Tensor& v, const at::Tensor& g,
+                        const c10::optional<at::Tensor>& pbf, double lr, double b1, double b2, double eps,
+                        const c10::optional<at::Tensor>& step, double grad_scale, int64_t t_offset, const std::string& lr_kind,
+                        const std::vector<double>& lr_params, const std::vector<int64_t>& lr_boundaries,
+                        const std::vector<double>& lr_values, const c10::optional<at::Tensor>& gscale,
+                        const c10::optional<at::Tensor>& ema, double ema_decay, bool ema_num_updates,
+                        const c10::optional<at::Tensor>& guard) {
+  check_params(p, who);
+  float* mp = slot_ptr(m, p, who, "m");
+  float* vp = slot_ptr(v, p, who, "v");
+  const GradPtr gp = grad_ptr(g, p, who);
+  uint16_t* pb = shadow_ptr(pbf, p, who);
+  const int64_t* step_p = step_ptr(step, p, who);
+  const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
+  TORCH_CHECK(sc.kind == LR_CONSTANT || step, who, ": a schedule needs the device step tensor");
+  TORCH_CHECK(!ema_num_updates || !ema || step, who, ": ema_num_updates needs the device step tensor");
+  const OptMods mods = flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard);
+  check_aligned(p.data_ptr(), 16, who, "p");
+  check_aligned(mp, 16, who, "m");
+  check_aligned(vp, 16, who, "v");
+  if (gp.f) check_aligned(gp.f, 16, who, "g");
+  if (gp.b) check_aligned(gp.b, 8, who, "g");
+  if (pb) check_aligned(pb, 8, who, "pbf");
+  if (mods.ema) check_aligned(mods.ema, 16, who, "ema");
+  return AdamCall{AdamArgs{(float*)p.data_ptr(), mp, vp, gp.f, pb, gp.b, p.numel(), sc, (float)b1, (float)b2, (float)eps,
+                           step_p, (int)t_offset, (float)grad_scale},
+                  mods};
+}
+
+// Adam's t = *step + t_offset (no step: t_offset); the schedule is evaluated on the device at s = t - 1
 void adam_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf, double lr,
-               double b1, double b2, double eps, at::Tensor step, double grad_scale, int64_t t_offset,
+               double b1, double b2, double eps, c10::optional<at::Tensor> step, double grad_scale, int64_t t_offset,
                std::string lr_kind, std::vector<double> lr_params, std::vector<int64_t> lr_boundaries,
                std::vector<double> lr_values, c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> ema,
                double ema_decay, bool ema_num_updates, c10::optional<at::Tensor> guard) {
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), "adam_flat: fp32 GPU params");
-  TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel() && g.numel() == p.numel(), "adam_flat: sizes");
-  TORCH_CHECK(step.scalar_type() == at::kLong && step.is_cuda(), "adam_flat: int64 GPU step");
-  const bool gb = g.scalar_type() == at::kBFloat16;
-  AdamArgs a{(float*)p.data_ptr(), (float*)m.data_ptr(), (float*)v.data_ptr(), gb ? nullptr : (const float*)g.data_ptr(),
-             pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-             flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values), (float)b1, (float)b2, (float)eps,
-             (const int64_t*)step.data_ptr(), (int)t_offset, (float)grad_scale};
-  adam_launch(a, flat_mods("adam_flat", p, gscale, ema, ema_decay, ema_num_updates, guard), cur());
+  const AdamCall c = adam_flat_args("adam_flat", p, m, v, g, pbf, lr, b1, b2, eps, step, grad_scale, t_offset, lr_kind,
+                                    lr_params, lr_boundaries, lr_values, gscale, ema, ema_decay, ema_num_updates, guard);
+  launch([&] { adam_launch(c.a, c.m, cur()); });
+}
+
+// The ranges form (adam_ranges_kernel: the ZeRO-1 optimizer's one launch over conv bucket + fc1 shard + tail) on
+// its own, for the tests: adam_flat's arguments, and up to 3 ranges [beg[k], beg[k] + n[k]) of the buffers, in
+// order and disjoint. Elements outside the ranges are not touched. The launcher refuses an unaligned range
+// (every beg and every n but the last a multiple of 4), a range count outside 1..3 and a guard.
+void adam_ranges_flat(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, c10::optional<at::Tensor> pbf,
+                      std::vector<int64_t> beg, std::vector<int64_t> n, double lr, double b1, double b2, double eps,
+                      c10::optional<at::Tensor> step, double grad_scale, int64_t t_offset, std::string lr_kind,
+                      std::vector<double> lr_params, std::vector<int64_t> lr_boundaries, std::vector<double> lr_values,
+                      c10::optional<at::Tensor> gscale, c10::optional<at::Tensor> ema, double ema_decay,
+                      bool ema_num_updates, c10::optional<at::Tensor> guard) {
+  const char* who = "adam_ranges_flat";
+  const AdamCall c = adam_flat_args(who, p, m, v, g, pbf, lr, b1, b2, eps, step, grad_scale, t_offset, lr_kind, lr_params,
+                                    lr_boundaries, lr_values, gscale, ema, ema_decay, ema_num_updates, guard);
+  TORCH_CHECK(beg.size() == n.size(), who, ": one n per beg, got ", beg.size(), " and ", n.size());
+  int64_t end = 0;
+  for (size_t k = 0; k < beg.size(); ++k) {
+    TORCH_CHECK(beg[k] >= end && n[k] >= 0 && n[k] <= p.numel() - beg[k], who, ": range ", k, " = [", beg[k], ", ", beg[k],
+                " + ", n[k], ") is not inside the buffers behind its predecessor");
+    end = beg[k] + n[k];
+  }
+  launch([&] { adam_launch_ranges(c.a, c.m, (int)beg.size(), beg.data(), n.data(), cur()); });
 }
 
 // what momentum_flat and momentum_ema_flat share: the checks both make and the kernel's arguments
@@ -41,15 +130,15 @@ SgdArgs sgd_flat_args(const char* who, at::Tensor& p, const c10::optional<at::Te
                       double grad_scale, const c10::optional<at::Tensor>& step, int64_t t_offset, const std::string& lr_kind,
                       const std::vector<double>& lr_params, const std::vector<int64_t>& lr_boundaries,
                       const std::vector<double>& lr_values) {
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(), who, ": fp32 GPU params");
-  TORCH_CHECK(!step || (step->scalar_type() == at::kLong && step->is_cuda()), who, ": int64 GPU step");
+  check_params(p, who);
+  float* mp = mom ? slot_ptr(*mom, p, who, "mom") : nullptr;
+  const GradPtr gp = grad_ptr(g, p, who);
+  uint16_t* pb = shadow_ptr(pbf, p, who);
+  const int64_t* step_p = step_ptr(step, p, who);
   const LrSchedule sc = flat_schedule(lr, lr_kind, lr_params, lr_boundaries, lr_values);
   TORCH_CHECK(sc.kind == LR_CONSTANT || step, who, ": a schedule needs the device step tensor");
-  const bool gb = g.scalar_type() == at::kBFloat16;
-  return SgdArgs{(float*)p.data_ptr(), mom ? (float*)mom->data_ptr() : nullptr, gb ? nullptr : (const float*)g.data_ptr(),
-                 pbf ? (uint16_t*)pbf->data_ptr() : nullptr, gb ? (const uint16_t*)g.data_ptr() : nullptr, p.numel(),
-                 sc, (float)momentum, (float)weight_decay, (float)grad_scale, nesterov ? 1 : 0,
-                 step ? (const int64_t*)step->data_ptr() : nullptr, (int)t_offset};
+  return SgdArgs{(float*)p.data_ptr(), mp, gp.f, pb, gp.b, p.numel(), sc, (float)momentum, (float)weight_decay,
+                 (float)grad_scale, nesterov ? 1 : 0, step_p, (int)t_offset};
 }
 
 void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c10::optional<at::Tensor> pbf,
@@ -60,7 +149,8 @@ void momentum_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g, c1
   const char* who = "momentum_flat";
   const SgdArgs a = sgd_flat_args(who, p, mom, g, pbf, lr, momentum, weight_decay, nesterov, grad_scale, step, t_offset,
                                   lr_kind, lr_params, lr_boundaries, lr_values);
-  sgd_launch(a, flat_mods(who, p, gscale, c10::nullopt, 0.0, false, guard), cur());
+  const OptMods mods = flat_mods(who, p, gscale, c10::nullopt, 0.0, false, guard);
+  launch([&] { sgd_launch(a, mods, cur()); });
 }
 
 // momentum_flat with the moving average of the weights updated by the same launch (csrc/ema.h): the
@@ -76,9 +166,8 @@ void momentum_ema_flat(at::Tensor p, c10::optional<at::Tensor> mom, at::Tensor g
   const SgdArgs a = sgd_flat_args(who, p, mom, g, pbf, lr, momentum, weight_decay, nesterov, grad_scale, step, t_offset,
                                   lr_kind, lr_params, lr_boundaries, lr_values);
   TORCH_CHECK(!ema_num_updates || step, who, ": ema_num_updates needs the device step tensor");
-  TORCH_CHECK(g.numel() == p.numel() && (!mom || mom->numel() == p.numel()) && (!pbf || pbf->numel() == p.numel()), who,
-              ": sizes");
-  sgd_launch(a, flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard), cur());
+  const OptMods mods = flat_mods(who, p, gscale, ema, ema_decay, ema_num_updates, guard);
+  launch([&] { sgd_launch(a, mods, cur()); });
 }
 
 // The shadow update as a pass of its own, from parameters already updated: e' = e - (1 - d_t)(e - p),
@@ -207,10 +296,16 @@ TORCH_LIBRARY(tfd, m) {
   m.def("crc32c(Tensor bytes, int init=0) -> int");
   m.impl("crc32c", c10::DispatchKey::CPU, &crc32c_op);
   m.def("adam_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, float lr, float b1, float b2, "
-        "float eps, Tensor(e!) step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
+        "float eps, Tensor? step, float grad_scale=1.0, int t_offset=1, str lr_kind=\"constant\", "
         "float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], Tensor? gscale=None, "
         "Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False, Tensor? guard=None) -> ()");
   m.impl("adam_flat", c10::DispatchKey::CUDA, &adam_flat);
+  m.def("adam_ranges_flat(Tensor(a!) p, Tensor(b!) m, Tensor(c!) v, Tensor g, Tensor(d!)? pbf, int[] beg, int[] n, "
+        "float lr, float b1, float b2, float eps, Tensor? step, float grad_scale=1.0, int t_offset=1, "
+        "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "
+        "Tensor? gscale=None, Tensor(f!)? ema=None, float ema_decay=0.0, bool ema_num_updates=False, "
+        "Tensor? guard=None) -> ()");
+  m.impl("adam_ranges_flat", c10::DispatchKey::CUDA, &adam_ranges_flat);
   m.def("momentum_flat(Tensor(a!) p, Tensor(b!)? mom, Tensor g, Tensor(d!)? pbf, float lr, float momentum, "
         "float weight_decay, bool nesterov, float grad_scale=1.0, Tensor? step=None, int t_offset=1, "
         "str lr_kind=\"constant\", float[] lr_params=[], int[] lr_boundaries=[], float[] lr_values=[], "

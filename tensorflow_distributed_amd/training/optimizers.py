@@ -15,7 +15,9 @@ Two layers:
 
 TF ApplyAdam: ``lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)``; ``m = m + (g - m)(1 - b1)``;
 ``v = v + (g^2 - v)(1 - b2)``; ``p -= lr_t * m / (sqrt(v) + eps)``, ``t`` = update count (the
-``beta1_power``/``beta2_power`` accumulators are ``b^t``).
+``beta1_power``/``beta2_power`` accumulators are ``b^t``). :func:`adam_update` and
+:func:`momentum_update` are the fp64 definitions of ApplyAdam and ApplyMomentum / GradientDescent that the
+flat kernels (``csrc/optim_kernels.h``) are held to element by element (``tests/flat_optim_oracle.py``).
 
 Learning-rate schedules (``tf.train.exponential_decay`` / ``piecewise_constant`` /
 ``polynomial_decay`` / ``cosine_decay``, each with an optional linear warm-up): the ``learning_rate``
@@ -369,6 +371,31 @@ def adagrad_update(p, accum, g, lr: float):
     p, accum, g = f(p), f(accum), f(g)
     a2 = accum + g * g
     return p - lr * g / a2.sqrt(), a2
+
+
+def adam_update(p, m, v, g, t: int, lr: float, beta1: float, beta2: float, epsilon: float):
+    """One Adam update in fp64 (TF1 ApplyAdam, as ``csrc/kernels/optim.hip`` states it): ``(p', m', v')``.
+    ``g`` is the gradient the optimizer consumes (scale and clip factor applied), ``t`` the update's count
+    (``global_step`` after it), ``lr`` the rate of this update; epsilon is outside the root."""
+    f = lambda x: torch.as_tensor(x).detach().to(torch.float64)  # noqa: E731
+    p, m, v, g = f(p), f(m), f(v), f(g)
+    m2 = m + (g - m) * (1.0 - beta1)
+    v2 = v + (g * g - v) * (1.0 - beta2)
+    lr_t = lr * math.sqrt(1.0 - beta2 ** int(t)) / (1.0 - beta1 ** int(t))
+    return p - lr_t * m2 / (v2.sqrt() + epsilon), m2, v2
+
+
+def momentum_update(p, accum, g, lr: float, momentum: float, weight_decay: float = 0.0, nesterov: bool = False):
+    """One Momentum update in fp64 (TF1 ApplyMomentum): ``(p', accum')`` with ``accum' = momentum accum + g`` and
+    ``p' = p - lr accum'``, Nesterov ``p' = p - lr (g + momentum accum')``. ``accum=None`` is plain gradient
+    descent, ``(p - lr g, None)``. The L2 weight decay is folded into the gradient: ``g + weight_decay p``."""
+    f = lambda x: torch.as_tensor(x).detach().to(torch.float64)  # noqa: E731
+    p, g = f(p), f(g)
+    g = g + weight_decay * p
+    if accum is None:
+        return p - lr * g, None
+    a2 = momentum * f(accum) + g
+    return p - lr * ((g + momentum * a2) if nesterov else a2), a2
 
 
 LW_DECAY, LW_ADAPT = 1, 2  # csrc/layerwise.h: LwFlags
