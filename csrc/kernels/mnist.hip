@@ -1500,17 +1500,25 @@ void mnist_forward_conv(const MnistStepArgs& a, hipStream_t s) {
   TFD_LAUNCH(conv12_fwd_lds<<<2 * a.B, 512, C12_SMEM, s>>>(CONV12_HOT(HOT_PASS) a));
 }
 
-void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
+// fc1 alone: the split-K slabs, for whichever head reduces them
+static void mnist_forward_fc1(const MnistStepArgs& a, hipStream_t s) {
   const int B = a.B;
-  {
-    constexpr int sm = GemmSmemOneshot<FC1_BM, FC1_BN, FC1_BK, FC1_NKT, DenseLoaderX<true>, DenseLoaderX<false>>::BYTES;
-    static_assert(sm <= 160 * 1024, "fc1 one-shot LDS");
-    set_smem<fc1_fwd>(sm);
-    const int kper = (FEAT + a.fc1_splits - 1) / a.fc1_splits;
-    dim3 g(HID / FC1_BN, (B + FC1_BM - 1) / FC1_BM, a.fc1_splits);
-    TFD_LAUNCH(fc1_fwd<<<g, 256, sm, s>>>(FC1F_HOT(HOT_PASS) kper, a));
-  }
-  TFD_LAUNCH(head_kernel<<<B, 256, 0, s>>>(HEAD_HOT(HOT_PASS) a, train ? 1 : 0));
+  constexpr int sm = GemmSmemOneshot<FC1_BM, FC1_BN, FC1_BK, FC1_NKT, DenseLoaderX<true>, DenseLoaderX<false>>::BYTES;
+  static_assert(sm <= 160 * 1024, "fc1 one-shot LDS");
+  set_smem<fc1_fwd>(sm);
+  const int kper = (FEAT + a.fc1_splits - 1) / a.fc1_splits;
+  dim3 g(HID / FC1_BN, (B + FC1_BM - 1) / FC1_BM, a.fc1_splits);
+  TFD_LAUNCH(fc1_fwd<<<g, 256, sm, s>>>(FC1F_HOT(HOT_PASS) kper, a));
+}
+
+void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s) {
+  mnist_forward_fc1(a, s);
+  TFD_LAUNCH(head_kernel<<<a.B, 256, 0, s>>>(HEAD_HOT(HOT_PASS) a, train ? 1 : 0));
+}
+
+void mnist_forward_nohead(const MnistStepArgs& a, hipStream_t s) {
+  mnist_forward_conv(a, s);
+  mnist_forward_fc1(a, s);
 }
 
 void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {

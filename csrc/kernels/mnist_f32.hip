@@ -799,7 +799,7 @@ int mnist_f32_max_batch() { return F_OUTG_MAX_B; }
 int mnist_f32_fc1_splits() { return F_FC1_SPLITS; }
 int mnist_f32_wg2_splits(int B) { return (B + F2W_IMG - 1) / F2W_IMG; }  // one slab per image pair
 
-void mnist_f32_forward(const MnistF32Args& a, bool train, hipStream_t s) {
+void mnist_f32_forward_nohead(const MnistF32Args& a, hipStream_t s) {
   const int B = a.B;
   set_smem_f<f32_conv12_fwd_lds>(F2F_SMEM);
   TFD_LAUNCH(f32_conv12_fwd_lds<<<2 * B, 512, F2F_SMEM, s>>>(a));
@@ -808,7 +808,11 @@ void mnist_f32_forward(const MnistF32Args& a, bool train, hipStream_t s) {
     set_smem_f<f32_fc1_fwd>(sm);
     TFD_LAUNCH(f32_fc1_fwd<<<dim3(HID / 64, (B + 63) / 64, F_FC1_SPLITS), 256, sm, s>>>(a));
   }
-  TFD_LAUNCH(f32_head<<<B, 256, 0, s>>>(a, train ? 1 : 0));
+}
+
+void mnist_f32_forward(const MnistF32Args& a, bool train, hipStream_t s) {
+  mnist_f32_forward_nohead(a, s);
+  TFD_LAUNCH(f32_head<<<a.B, 256, 0, s>>>(a, train ? 1 : 0));
 }
 
 void mnist_f32_backward(const MnistF32Args& a, hipStream_t s) {

@@ -22,6 +22,7 @@
 #include "../ema.h"
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
+#include "../mnist_infer.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
 #include "../optim_rules.h"
@@ -1189,6 +1190,101 @@ class MnistEngine : public torch::CustomClassHolder {
     return out;
   }
 
+  // ---- device inference (csrc/mnist_infer.h) ----
+  // The forward up to fc1 as evaluate() runs it, then the inference head, which stores the logits and
+  // classes into buffers of its own: loss_rows(), correct_rows(), dlogits(), the prefetch buffers and
+  // every piece of training state keep their bits.
+  //
+  // predict: x [n,784] fp32, y an empty tensor or [n] int32, both on the engine's device and
+  // contiguous; rows in chunks of <= B. Returns (logits [n,10] fp32, classes [n] int32, loss_rows [n],
+  // correct_rows [n]); the last two are empty without labels. use_ema as in evaluate().
+  std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> predict(at::Tensor x, at::Tensor y, bool use_ema) {
+    check_rows("predict: x", x, at::kFloat, 2);
+    TORCH_CHECK(x.size(1) == 784, "predict: x must be [n,784], got [", x.size(0), ",", x.size(1), "]");
+    const int64_t n = x.size(0);
+    const bool labelled = y.numel() > 0;
+    if (labelled) {
+      check_rows("predict: y", y, at::kInt, 1);
+      TORCH_CHECK(y.size(0) == n, "predict: y has ", y.size(0), " labels for ", n, " rows");
+    }
+    TORCH_CHECK(!use_ema || ema_on(), "predict(use_ema): set_ema first");
+    auto logits = at::empty({n, NCLS}, x.options());
+    auto classes = at::empty({n}, x.options().dtype(at::kInt));
+    auto loss = at::empty({labelled ? n : 0}, x.options());
+    auto correct = at::empty({labelled ? n : 0}, x.options());
+    if (n == 0) return {logits, classes, loss, correct};
+    refresh_ema_image(use_ema, stream());
+    for (int64_t o = 0; o < n; o += B_) {
+      const int nb = (int)std::min<int64_t>(B_, n - o);
+      InferHeadArgs h = infer_forward((const float*)x.data_ptr() + o * 784, nb, use_ema, stream());
+      h.labels = labelled ? (const int*)y.data_ptr() + o : nullptr;
+      h.logits = (float*)logits.data_ptr() + o * NCLS;
+      h.classes = (int*)classes.data_ptr() + o;
+      h.loss_row = labelled ? (float*)loss.data_ptr() + o : nullptr;
+      h.correct_row = labelled ? (float*)correct.data_ptr() + o : nullptr;
+      infer_head(h, !fp32_, stream());
+    }
+    return {logits, classes, loss, correct};
+  }
+
+  // A device-resident evaluation split, uploaded once: images [N,784] fp32, labels [N] int32 in
+  // [0, 10) (checked here: one synchronisation). Graphs captured over an earlier split are dropped.
+  void set_eval_dataset(at::Tensor images, at::Tensor labels) {
+    check_rows("set_eval_dataset: images", images, at::kFloat, 2);
+    check_rows("set_eval_dataset: labels", labels, at::kInt, 1);
+    TORCH_CHECK(images.size(1) == 784 && labels.size(0) == images.size(0), "set_eval_dataset: images [N,784], labels [N]");
+    if (labels.numel() > 0) {
+      const int64_t lo = labels.min().item<int64_t>(), hi = labels.max().item<int64_t>();
+      TORCH_CHECK(lo >= 0 && hi < NCLS, "set_eval_dataset: labels must be in [0, ", NCLS, "), got [", lo, ", ", hi, "]");
+    }
+    for (auto& kv : eval_recs_) drop_graph(kv.first);
+    eval_recs_.clear();
+    eval_x_ = images;
+    eval_y_ = labels;
+    if (!inf_logits_.defined()) {
+      inf_logits_ = at::empty({B_, NCLS}, loss_row_.options());
+      inf_classes_ = at::empty({B_}, ybuf_.options());
+      inf_loss_ = at::empty({B_}, loss_row_.options());
+      inf_correct_ = at::empty({B_}, loss_row_.options());
+    }
+  }
+  int64_t eval_dataset_rows() const { return eval_x_.defined() ? eval_x_.size(0) : 0; }
+
+  // Rows [first, first + count) of the evaluation split in groups of `group` rows, each group in
+  // chunks of <= B: one record per group (mnist_infer.h), fp64 [ceil(count / group)][104] on the device.
+  at::Tensor evaluate_dataset(int64_t first, int64_t count, int64_t group, bool use_ema) {
+    check_eval_range("evaluate_dataset", first, count, group, use_ema);
+    auto rec = at::empty({(count + group - 1) / group, kEvalRecFields}, eval_x_.options().dtype(at::kDouble));
+    if (count == 0) return rec;
+    refresh_ema_image(use_ema, stream());
+    eval_launches(first, count, group, use_ema, (double*)rec.data_ptr(), stream());
+    return rec;
+  }
+  // The same launches as ONE hipGraph, replayed with replay(name, 1); the records are eval_records(name),
+  // allocated here, outside the capture. With use_ema in bf16 the graph's first node casts the fp32
+  // shadow to the bf16 image the forward reads, so a replay always sees the current averages. The
+  // first chunk's forward runs once eagerly before the capture: the launchers raise their kernels'
+  // dynamic-LDS limits at their first launch, which belongs outside a capture.
+  void capture_eval(const std::string& name, int64_t first, int64_t count, int64_t group, bool use_ema) {
+    check_eval_range("capture_eval", first, count, group, use_ema);
+    TORCH_CHECK(count > 0, "capture_eval: count > 0");
+    hipStream_t s = capture_stream();
+    drop_graph(name);
+    auto rec = at::empty({(count + group - 1) / group, kEvalRecFields}, eval_x_.options().dtype(at::kDouble));
+    if (use_ema && !fp32_ && !ema_bf_.defined()) ema_bf_ = at::empty_like(pbf_);
+    (void)infer_forward((const float*)eval_x_.data_ptr() + first * 784, (int)std::min(std::min(B_, group), count), false, s);
+    StreamCapture cap(s);
+    if (use_ema && !fp32_) cast_f32_bf16((const float*)ema_.data_ptr(), (uint16_t*)ema_bf_.data_ptr(), TOTAL, s);
+    eval_launches(first, count, group, use_ema, (double*)rec.data_ptr(), s);
+    store_graph(name, cap);
+    eval_recs_[name] = rec;
+  }
+  at::Tensor eval_records(const std::string& name) {
+    auto it = eval_recs_.find(name);
+    TORCH_CHECK(it != eval_recs_.end(), "eval_records: no evaluation graph named ", name);
+    return it->second;
+  }
+
   // ---- hipGraph capture / replay of the whole step ----
   void capture_train_step(const std::string& name) { capture_train_steps(name, 1); }
   // n consecutive steps in ONE graph: the step counter, the dataset cursor and the dropout key all
@@ -1666,6 +1762,79 @@ class MnistEngine : public torch::CustomClassHolder {
     }
   }
 
+  // ---- device inference ----
+  // an operand of predict / set_eval_dataset, checked before the first launch: on the engine's device,
+  // of the dtype and rank asked, contiguous
+  void check_rows(const char* what, const at::Tensor& t, at::ScalarType dt, int64_t dim) const {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == device_, what, " must be on cuda:", device_);
+    TORCH_CHECK(t.scalar_type() == dt, what, " must be ", dt, ", got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == dim, what, " must have ", dim, " dimension(s), got ", t.dim());
+    TORCH_CHECK(t.is_contiguous(), what, " must be contiguous");
+  }
+  void check_eval_range(const char* what, int64_t first, int64_t count, int64_t group, bool use_ema) const {
+    TORCH_CHECK(eval_x_.defined(), what, ": set_eval_dataset first");
+    TORCH_CHECK(first >= 0 && count >= 0 && first + count <= eval_x_.size(0), what, ": rows [", first, ", ", first + count,
+                ") outside the evaluation split of ", eval_x_.size(0), " rows");
+    TORCH_CHECK(group >= 1, what, ": group >= 1, got ", group);
+    TORCH_CHECK(!use_ema || ema_on(), what, "(use_ema): set_ema first");
+  }
+  // evaluate(use_ema)'s staleness rule for the bf16 image of the shadow
+  void refresh_ema_image(bool use_ema, hipStream_t s) {
+    if (!use_ema || fp32_) return;
+    if (!ema_bf_.defined()) ema_bf_ = at::empty_like(pbf_);
+    if (ema_bf_stale_) cast_f32_bf16((const float*)ema_.data_ptr(), (uint16_t*)ema_bf_.data_ptr(), TOTAL, s);
+    ema_bf_stale_ = false;
+  }
+  // conv1, conv2 and fc1 over nb <= B fed rows at x, as evaluate() runs them; returns the inference
+  // head's view of the slabs and the parameters (the caller sets the labels and the outputs)
+  InferHeadArgs infer_forward(const float* x, int nb, bool use_ema, hipStream_t s) {
+    InferHeadArgs h{};
+    h.rows = nb;
+    h.split_rows = nb;
+    h.p32 = (const float*)(use_ema ? ema_ : params_).data_ptr();
+    MnistStepArgs a = args();
+    a.B = nb;
+    a.data = x;
+    a.labels = nullptr;
+    a.perm = nullptr;
+    if (use_ema) {
+      a.p32 = h.p32;
+      if (!fp32_) a.pbf = (const uint16_t*)ema_bf_.data_ptr();
+    }
+    if (fp32_) {
+      MnistF32Args f = args_f32(a);
+      mnist_f32_forward_nohead(f, s);
+      h.fc1_slab = f.fc1_slab;
+      h.splits = f.fc1_splits;
+    } else {
+      mnist_forward_nohead(a, s);
+      h.fc1_slab = a.fc1_slab;
+      h.splits = a.fc1_splits;
+    }
+    return h;
+  }
+  void eval_launches(int64_t first, int64_t count, int64_t group, bool use_ema, double* rec, hipStream_t s) {
+    const float* x = (const float*)eval_x_.data_ptr();
+    const int* y = (const int*)eval_y_.data_ptr();
+    for (int64_t g0 = 0, gi = 0; g0 < count; g0 += group, ++gi) {
+      const int64_t gn = std::min(group, count - g0);
+      for (int64_t o = 0; o < gn; o += B_) {
+        const int nb = (int)std::min<int64_t>(B_, gn - o);
+        const int64_t r = first + g0 + o;
+        InferHeadArgs h = infer_forward(x + r * 784, nb, use_ema, s);
+        h.labels = y + r;
+        h.logits = (float*)inf_logits_.data_ptr();
+        h.classes = (int*)inf_classes_.data_ptr();
+        h.loss_row = (float*)inf_loss_.data_ptr();
+        h.correct_row = (float*)inf_correct_.data_ptr();
+        infer_head(h, !fp32_, s);
+        EvalReduceArgs e{nb, h.labels, h.classes, h.loss_row, h.correct_row, rec + gi * kEvalRecFields,
+                         o == 0 ? EVAL_STORE : EVAL_ADD};
+        eval_reduce(e, s);
+      }
+    }
+  }
+
   MnistF32Args args_f32() { return args_f32(args()); }
   // the fp32 kernels' view of a step's arguments
   MnistF32Args args_f32(const MnistStepArgs& a) {
@@ -1824,6 +1993,10 @@ class MnistEngine : public torch::CustomClassHolder {
   bool ema_nu_ = false;
   at::Tensor ema_, ema_bf_, one_;
   bool ema_bf_stale_ = true;
+  // device inference: the evaluation split (set_eval_dataset), the inference head's own per-chunk
+  // outputs, and the record array of every captured evaluation graph
+  at::Tensor eval_x_, eval_y_, inf_logits_, inf_classes_, inf_loss_, inf_correct_;
+  std::map<std::string, at::Tensor> eval_recs_;
   std::map<std::string, hipGraphExec_t> graphs_;
   // capture_topology: nodes added by each tagged operation (label@step -> node handles)
   bool topo_ = false;
@@ -1942,6 +2115,14 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("reduce_grads", &MnistEngine::reduce_grads)
       .def("train_step", &MnistEngine::train_step)
       .def("evaluate", &MnistEngine::evaluate, "", {torch::arg("x"), torch::arg("y"), torch::arg("use_ema") = false})
+      .def("predict", &MnistEngine::predict, "", {torch::arg("x"), torch::arg("y"), torch::arg("use_ema") = false})
+      .def("set_eval_dataset", &MnistEngine::set_eval_dataset)
+      .def("eval_dataset_rows", &MnistEngine::eval_dataset_rows)
+      .def("evaluate_dataset", &MnistEngine::evaluate_dataset, "",
+           {torch::arg("first"), torch::arg("count"), torch::arg("group"), torch::arg("use_ema") = false})
+      .def("capture_eval", &MnistEngine::capture_eval, "",
+           {torch::arg("name"), torch::arg("first"), torch::arg("count"), torch::arg("group"), torch::arg("use_ema") = false})
+      .def("eval_records", &MnistEngine::eval_records)
       .def("capture_train_step", &MnistEngine::capture_train_step)
       .def("capture_train_steps", &MnistEngine::capture_train_steps)
       .def("capture_grads", &MnistEngine::capture_grads)

@@ -77,6 +77,8 @@ int mnist_wg2_splits(int B);
 void mnist_forward(const MnistStepArgs& a, bool train, hipStream_t s);        // conv1, conv2, fc1, head
 void mnist_forward_conv(const MnistStepArgs& a, hipStream_t s);               // conv1, conv2 (read region B)
 void mnist_forward_fc(const MnistStepArgs& a, bool train, hipStream_t s);     // fc1, head (read region A)
+// conv1, conv2, fc1: the forward up to the split-K slabs, for the inference head (mnist_infer.h)
+void mnist_forward_nohead(const MnistStepArgs& a, hipStream_t s);
 // fc1 dW/dX + out-layer grads. part 0: one launch; part 1: dW + out grads (bucket A complete);
 // part 2: dX (DP launches 1 then 2 so bucket A's all-reduce starts before the dX GEMM)
 void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part = 0);
@@ -138,6 +140,7 @@ struct MnistF32Args {
 int mnist_f32_fc1_splits();
 int mnist_f32_wg2_splits(int B);
 void mnist_f32_forward(const MnistF32Args& a, bool train, hipStream_t s);
+void mnist_f32_forward_nohead(const MnistF32Args& a, hipStream_t s);  // conv1, conv2, fc1 (mnist_infer.h)
 void mnist_f32_backward(const MnistF32Args& a, hipStream_t s);  // fc + conv grads (slabs for conv)
 
 // ---------------- optimizers (flat, fp32 master + bf16 shadow) ----------------

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -20,7 +20,7 @@ import torch  # noqa: E402
 
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
-from tensorflow_distributed_amd.training import checkpoint  # noqa: E402
+from tensorflow_distributed_amd.training import checkpoint, inference  # noqa: E402
 from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
 from tensorflow_distributed_amd.training.optimizers import (AdagradOptimizer, AdamOptimizer, LAMBOptimizer,  # noqa: E402
                                                             LARSOptimizer, RMSPropOptimizer)
@@ -86,6 +86,12 @@ def main(argv=None):
                     "round trip. N > 1 replays N steps as one captured graph and reads their losses once per call from "
                     "the device step log; a call also ends at every --display_step multiple (the minibatch-loss forward "
                     "needs the last batch). GPU with the device-resident split only; 1 = one step per call")
+    ap.add_argument("--device_eval", action="store_true", help="upload the validation split once and evaluate it on "
+                    "the device: the --eval_batches x 100 rows in split order (not next_batch's shuffle: the same mean "
+                    "whenever they are the whole split, as the default 50 x 100 are), one record per batch folded by the "
+                    "engine (GPU: one replayed graph, one read-back); off = the host-fed loop")
+    ap.add_argument("--confusion_matrix", action="store_true", help="--device_eval: print the 10 x 10 confusion matrix "
+                    "and the per-class recall and precision of the validation pass")
     ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
                     "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
@@ -102,6 +108,8 @@ def main(argv=None):
             ap.error("--steps_per_call > 1 with --host_feed: a host-fed batch crosses to the device before every step")
         if a.no_graph:
             ap.error("--steps_per_call > 1 with --no_graph: the steps of a call are one captured graph")
+    if a.confusion_matrix and not a.device_eval:
+        ap.error("--confusion_matrix is folded by --device_eval: give both")
     step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
@@ -193,12 +201,20 @@ def main(argv=None):
     if a.ema_decay > 0:
         print("Accuracy from the %s" % ("moving averages (decay %g)" % a.ema_decay if use_ema else "variables"))
     accuracy_arr = []
-    for counter in range(1, nt + 1):
-        val_x, val_y = mnist.validation.next_batch(100)
-        _, correct = runner.evaluate(val_x, val_y, use_ema=use_ema)
-        accuracy_arr.append(correct / float(len(val_x)))
+    if a.device_eval:
+        # the split uploaded once, rows in split order; one record per batch of 100 from one call
+        runner.set_eval_dataset(mnist.validation.images, mnist.validation.labels)
+        recs = runner.evaluate_dataset(0, min(nt * 100, mnist.validation.num_examples), 100, use_ema=use_ema)
+        accuracy_arr = [r["correct"] / float(r["rows"]) for r in recs]
+    else:
+        for counter in range(1, nt + 1):
+            val_x, val_y = mnist.validation.next_batch(100)
+            _, correct = runner.evaluate(val_x, val_y, use_ema=use_ema)
+            accuracy_arr.append(correct / float(len(val_x)))
     mean_accuracy = sum(accuracy_arr) / len(accuracy_arr)
     print("Mean Accuracy : %f" % mean_accuracy)
+    if a.confusion_matrix:
+        print(inference.format_confusion(inference.merge_records(recs)["confusion"]))
     testing_end_time = time.time()
     print("--- %s seconds Time for Inference ---" % (testing_end_time - training_end_time))
     return 0

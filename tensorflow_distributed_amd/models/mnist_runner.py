@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from ..training.optimizers import (FlatApplier, base_optimizer, ema_decay_at, is_layerwise, is_schedule, lr_at,
                                    schedule_args)
+from ..training import inference
 from . import mnist_cnn as M
 
 
@@ -55,6 +56,35 @@ def _labels_to_ids(y) -> torch.Tensor:
 def _as_f32(x) -> torch.Tensor:
     x = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
     return x.reshape(x.shape[0], -1).to(torch.float32)
+
+
+def _as_rows(x) -> torch.Tensor:
+    """``_as_f32`` that also takes no rows at all ([0, ...] has no width to infer)."""
+    x = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
+    return _as_f32(x) if x.numel() else torch.zeros(0, 784, dtype=torch.float32)
+
+
+def _check_eval_split(images, labels):
+    x, y = _as_rows(images), _labels_to_ids(labels)
+    if x.dim() != 2 or x.shape[1] != 784 or y.dim() != 1 or y.shape[0] != x.shape[0]:
+        raise ValueError(f"set_eval_dataset: images [N,784] and labels [N], got {tuple(x.shape)} and {tuple(y.shape)}")
+    if y.numel() and (int(y.min()) < 0 or int(y.max()) >= M.NCLS):
+        raise ValueError(f"set_eval_dataset: labels must be in [0, {M.NCLS}), got [{int(y.min())}, {int(y.max())}]")
+    return x.contiguous(), y.contiguous()
+
+
+def _eval_range(split, first, count, group):
+    if split is None:
+        raise ValueError("evaluate_dataset: set_eval_dataset first")
+    n = split.shape[0]
+    first = int(first)
+    count = n - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > n:
+        raise ValueError(f"evaluate_dataset: rows [{first}, {first + count}) outside the evaluation split of {n} rows")
+    group = max(count, 1) if group is None else int(group)
+    if group < 1:
+        raise ValueError(f"evaluate_dataset: group >= 1, got {group}")
+    return first, count, group
 
 
 class MnistRunnerBase:
@@ -380,6 +410,39 @@ class TorchMnistRunner(MnistRunnerBase):
         logits = self._forward(x, 1.0, flat=self.ema_params() if use_ema else None)
         loss = F.cross_entropy(logits, y, reduction="sum").item()
         return float(loss), int((logits.argmax(1) == y).sum().item())
+
+    # ---- inference (training/inference.py holds the definitions) ----
+    _PREDICT_CHUNK = 1000  # rows per forward: bounds the activations of a whole split
+
+    @torch.no_grad()
+    def predict(self, x, use_ema: bool = False):
+        """``(logits [n,10] fp32, classes [n] int32)``: the forward without dropout; a row's class is the
+        first maximum of its logits. ``use_ema``: the moving averages in place of the parameters."""
+        x = _as_rows(x).to(self.device)
+        flat = self.ema_params() if use_ema else None
+        parts = [self._forward(x[o:o + self._PREDICT_CHUNK], 1.0, flat=flat)
+                 for o in range(0, x.shape[0], self._PREDICT_CHUNK)]
+        logits = torch.cat(parts) if parts else torch.zeros(0, M.NCLS, device=self.device)
+        # numpy's argmax returns the first maximum; torch's makes no promise about ties
+        classes = torch.from_numpy(logits.cpu().numpy().argmax(1).astype(np.int32)) if len(parts) else \
+            torch.zeros(0, dtype=torch.int32)
+        return logits, classes.to(self.device)
+
+    def set_eval_dataset(self, images, labels) -> None:
+        """Keep an evaluation split for ``evaluate_dataset``; labels outside [0, 10) are refused."""
+        self._eval_x, self._eval_y = _check_eval_split(images, labels)
+
+    def evaluate_dataset(self, first: int = 0, count: Optional[int] = None, group: Optional[int] = None,
+                         use_ema: bool = False) -> list:
+        """Records ``{loss_sum, rows, correct, confusion}`` of rows ``[first, first + count)`` of the
+        evaluation split, one per group of ``group`` rows (default: all of them in one group)."""
+        first, count, group = _eval_range(getattr(self, "_eval_x", None), first, count, group)
+        out = []
+        for g0 in range(first, first + count, group):
+            g1 = min(g0 + group, first + count)
+            logits, _ = self.predict(self._eval_x[g0:g1], use_ema)
+            out.append(inference.eval_record(logits.cpu().numpy(), self._eval_y[g0:g1].numpy()))
+        return out
 
 
 class NativeMnistRunner(MnistRunnerBase):
@@ -846,6 +909,51 @@ class NativeMnistRunner(MnistRunnerBase):
         self.stream.synchronize()
         r = r.cpu()
         return float(r[0]), int(round(float(r[1])))
+
+    # ---- device inference (csrc/mnist_infer.h) ----
+    def predict(self, x, use_ema: bool = False):
+        """``(logits [n,10] fp32, classes [n] int32)`` on the device: the forward up to fc1 and the
+        inference head, rows in chunks of the engine's batch. ``use_ema`` as in ``evaluate``."""
+        x = _as_rows(x).to(self.device).contiguous()
+        none = torch.empty(0, dtype=torch.int32, device=self.device)
+        with torch.cuda.stream(self.stream):
+            logits, classes, _, _ = self.eng.predict(x, none, bool(use_ema))
+        self.stream.synchronize()
+        return logits, classes
+
+    def set_eval_dataset(self, images, labels) -> None:
+        """Upload an evaluation split once; ``evaluate_dataset`` reads it on the device. Labels outside
+        [0, 10) are refused."""
+        x, y = _check_eval_split(images, labels)
+        self.stream.synchronize()  # the engine drops its evaluation graphs: none may still be running
+        with torch.cuda.stream(self.stream):
+            self._eval_x = x.to(self.device).contiguous()
+            self._eval_y = y.to(self.device).contiguous()
+            self.eng.set_eval_dataset(self._eval_x, self._eval_y)
+        self.stream.synchronize()
+        self._eval_graphs = set()
+
+    def evaluate_dataset(self, first: int = 0, count: Optional[int] = None, group: Optional[int] = None,
+                         use_ema: bool = False) -> list:
+        """Records ``{loss_sum, rows, correct, confusion}`` of rows ``[first, first + count)`` of the
+        evaluation split, one per group of ``group`` rows (default: all of them in one group), folded on
+        the device. With ``use_graph`` the whole pass is one hipGraph per ``(first, count, group,
+        use_ema)``, captured at its first use: a call is one replay, one synchronisation and one copy."""
+        first, count, group = _eval_range(getattr(self, "_eval_x", None), first, count, group)
+        if count == 0:
+            return []
+        with torch.cuda.stream(self.stream):
+            if self.use_graph:
+                name = "eval:%d:%d:%d:%d" % (first, count, group, int(bool(use_ema)))
+                if name not in self._eval_graphs:
+                    self.eng.capture_eval(name, first, count, group, bool(use_ema))
+                    self._eval_graphs.add(name)
+                self.eng.replay(name, 1)
+                rec = self.eng.eval_records(name)
+            else:
+                rec = self.eng.evaluate_dataset(first, count, group, bool(use_ema))
+        self.stream.synchronize()
+        return [inference.record_from_device(r) for r in rec.cpu().numpy()]
 
 
 def make_runner(batch_size: int, optimizer, device: torch.device, keep_prob: float = 0.75, seed: int = 0,

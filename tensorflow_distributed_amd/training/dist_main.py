@@ -20,7 +20,7 @@ import os
 import sys
 import tempfile
 import time
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -139,6 +139,13 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_boolean("use_graph", True, "Replay the captured hipGraph of the train step (GPU)")
     f.DEFINE_integer("eval_batches", 5, "Validation batches after training")
     f.DEFINE_integer("eval_batch_size", 1000, "Validation batch size")
+    f.DEFINE_boolean("device_eval", False, "Evaluate on the device: the validation split is uploaded once and the "
+                     "final pass and every --eval_at_steps row are one evaluate_dataset over its first --eval_batches x "
+                     "--eval_batch_size rows, in split order (not next_batch's shuffle: the same mean whenever they are "
+                     "the whole split, as the default 5 x 1000 are), one record per batch folded by the engine (GPU: "
+                     "one replayed graph, one read-back). --model mnist_cnn, synchronous all-reduce training")
+    f.DEFINE_boolean("confusion_matrix", False, "--device_eval: print the 10 x 10 confusion matrix and the per-class "
+                     "recall and precision of the final pass; the metrics file's evaluation record carries them")
     f.DEFINE_string("metrics_file", "", "Chief: JSONL metrics per step")
     f.DEFINE_string("trace_file", "", "Chrome-trace JSON of host step phases")
     f.DEFINE_integer("check_consistency_every", 0, "Every N steps all-reduce a param checksum and "
@@ -388,6 +395,25 @@ def check_steps_per_call_flags(num_workers: int) -> None:
         raise ValueError("%s with --use_graph=False: the N steps of a call are one captured graph" % which)
 
 
+def check_device_eval_flags(num_workers: int) -> None:
+    """--device_eval evaluates on the worker's engine from a split uploaded once; --confusion_matrix prints
+    what its records hold. What they do not cover is a flag error, raised before any process group is built."""
+    if FLAGS.confusion_matrix and not FLAGS.device_eval:
+        raise ValueError("--confusion_matrix without --device_eval: the matrix is folded by the device evaluation; "
+                         "give both")
+    if not FLAGS.device_eval:
+        return
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--device_eval with --model %s: the ResNet runner has no device inference" % FLAGS.model)
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts)):
+        raise ValueError("--device_eval in the parameter-server role (--sync_replicas=False, or backup workers with "
+                         "--ps_hosts): the variables live on the ps tasks and the worker's engine holds a copy that is "
+                         "fetched step by step; evaluate those runs with the host-fed pass")
+    if FLAGS.eval_batches < 1 or FLAGS.eval_batch_size < 1:
+        raise ValueError("--device_eval: --eval_batches and --eval_batch_size must be >= 1")
+
+
 def check_ema_flags(num_workers: int) -> None:
     """--ema_decay averages the variables of synchronous all-reduce training, where every worker holds
     them whole. The combinations it does not cover are flag errors, raised before any process group is
@@ -506,11 +532,12 @@ def _training_ends(time_begin: float, not_training: float = 0.0) -> float:
     return training_time
 
 
-def _validate(eval_batch) -> float:
+def _validate(eval_batch, batches: Optional[int] = None) -> float:
     """The reference's validation pass (5 x 1000 images, mnist_python_m.py:309-320) over --eval_batches
-    batches; ``eval_batch()`` evaluates the next one -> (images, correct). Returns the mean accuracy."""
+    batches (or ``batches`` of them); ``eval_batch()`` evaluates the next one -> (images, correct). Returns
+    the mean accuracy."""
     accs = []
-    for _ in range(FLAGS.eval_batches):
+    for _ in range(FLAGS.eval_batches if batches is None else batches):
         n, correct = eval_batch()
         print("After %d training step(s)", FLAGS.train_steps)  # verbatim reference line (quirk Q3)
         print("Accuracy : %f" % (correct / float(n)))
@@ -827,6 +854,7 @@ def main(argv=None) -> int:
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
     check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))
+    check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -881,6 +909,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     from ..models.mnist_runner import make_runner
     from ..utils.metrics import MetricsLogger, StepTimer, performance_table
     from ..utils.tracing import Watchdog, trace_range
+    from . import inference
     from .grad_sync import make_grad_sync
     from .optimizers import ExponentialMovingAverage, SyncReplicasOptimizer, ema_decay_at, lr_at
     from .step_calls import call_lengths, multiples
@@ -951,6 +980,17 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
         return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
 
+    eval_rows = min(FLAGS.eval_batches * FLAGS.eval_batch_size, mnist.validation.num_examples)
+    if FLAGS.device_eval:
+        runner.set_eval_dataset(mnist.validation.images, mnist.validation.labels)  # uploaded once
+
+    def eval_pass():
+        """One validation pass -> [(images, correct)] per batch and, with --device_eval, its records."""
+        if not FLAGS.device_eval:
+            return [eval_batch() for _ in range(FLAGS.eval_batches)], None
+        recs = runner.evaluate_dataset(0, eval_rows, FLAGS.eval_batch_size, use_ema=ema_eval)
+        return [(r["rows"], r["correct"]) for r in recs], recs
+
     def after_step(step: int, local_step: int) -> None:
         """What follows a step -- or, with --steps_per_call, a call's last step -- on the host."""
         nonlocal eval_time
@@ -973,7 +1013,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
             sv.on_step(step)
         while is_chief and eval_at and step >= eval_at[0]:
             te = time.time()
-            accs = [correct / float(n) for n, correct in (eval_batch() for _ in range(FLAGS.eval_batches))]
+            accs = [correct / float(n) for n, correct in eval_pass()[0]]
             acc = 100.0 * sum(accs) / len(accs)
             eval_time += time.time() - te
             row = dict(steps=eval_at.pop(0), time=time.time() - time_begin - eval_time, accuracy=round(acc, 2),
@@ -1090,7 +1130,20 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     print("Worker %d: %.1f images/sec (%d optimizer steps of %d images)" % (
         FLAGS.task_index, step_rows * (num_workers if sync else 1) * local_step / max(training_time, 1e-9), local_step,
         step_rows * (num_workers if sync else 1)))
-    mean_accuracy = _validate(eval_batch)
+    if FLAGS.device_eval:
+        batches, recs = eval_pass()
+        mean_accuracy = _validate(iter(batches).__next__, len(batches))
+        whole = inference.merge_records(recs)
+        evaluation = dict(event="evaluation", global_step=step, rows=whole["rows"], correct=whole["correct"],
+                          loss=whole["loss_sum"] / max(whole["rows"], 1), mean_accuracy=mean_accuracy)
+        if FLAGS.confusion_matrix:
+            print(inference.format_confusion(whole["confusion"]))
+            evaluation.update(confusion=whole["confusion"].tolist(),
+                              per_class_recall=[None if r != r else round(float(r), 6)
+                                                for r in inference.per_class_recall(whole["confusion"])])
+        metrics.log(**evaluation)
+    else:
+        mean_accuracy = _validate(eval_batch)
     skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
     if skipped > 0:
         print("Worker %d: --skip_nonfinite skipped %d of %d optimizer steps (aggregated gradient not finite)"
