@@ -990,15 +990,24 @@ __device__ __forceinline__ uint4 buf_ld_so(const uint16_t* base, uint32_t nbytes
   const i32x4v v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
   return make_uint4((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3]);
 }
-// W2 streams through a two-stage LDS ring of C2D_TPS taps (20 KB a stage) instead of staying whole
-// (100 KB): at 69.6 KB two blocks (dgrad or wgrad) share a CU, so the launch's 512 blocks are all
-// resident at once and one block's staging waits overlap the other's MFMA phases
+// W2 streams through an LDS ring of RING one-tap slots (4 KB each; tap T lives in slot T % RING) in
+// groups of TPS taps instead of staying whole (100 KB): under 80 KB two blocks (dgrad or wgrad) share
+// a CU, so the launch's 512 blocks are all resident at once and one block's staging waits overlap the
+// other's MFMA phases. RING / TPS groups are in flight or in use at a time: the barrier in front of
+// group g publishes it and frees group g - 1's slots, which group g - 1 + RING / TPS then streams
+// into, so a group is requested RING / TPS - 1 groups of MFMAs before its barrier. Two groups of 5 taps:
+// a group's barrier waits 70-150 cycles for its DMA (profiles/mnist_c2d_ring_stamps.txt), so deeper
+// rings (12 slots in groups of 4, 3, 2, 1) only added barriers and LDS and lost (docs/DESIGN.md 8d).
+// <25, 25> is the resident form (every tap up front, no ring, one block per CU): the tests' reference.
 #ifndef C2D_TPS
 #define C2D_TPS 5
 #endif
-constexpr int C2D_NST = 25 / C2D_TPS, C2D_WSTAGE = C2D_TPS * 32 * 64;  // stages, elements per stage
-static_assert(C2D_NST * C2D_TPS == 25 && C2D_WSTAGE % 512 == 0, "whole W2 stages of 1-KB DMA rows");
-constexpr int C2D_SMEM = (8 * C2D_PLANE * 8 + 2 * C2D_WSTAGE) * 2;  // 69,632 B
+#ifndef C2D_RING
+#define C2D_RING 10
+#endif
+constexpr int C2D_WTAP = 32 * 64;  // elements of one tap's [ci][co] rows: 4 DMA wave instructions, one per wave
+constexpr int c2d_smem(int ring) { return (8 * C2D_PLANE * 8 + ring * C2D_WTAP) * 2; }
+constexpr int C2D_SMEM = c2d_smem(C2D_RING);  // 69,632 B
 static_assert(2 * C2D_SMEM <= 160 * 1024, "two conv2_bwd_lds blocks share a CU (the launch's point)");
 static_assert(C2D_PLANE * 16 % 256 == 0 && C2D_PLANE >= C2D_ROWS * C2D_COLS, "dz2 plane");
 constexpr int C2D_X_OFF = 8 * C2D_PLANE * 8 * 2;          // 28672: the fused tail's buffers (dead weight region)
@@ -1023,37 +1032,50 @@ __device__ __forceinline__ int c1w_dz(int px, int c) {  // element offset of dz1
   do {                                                                                                   \
     if (TFD_STAMP && a.dbg && threadIdx.x == 0) a.dbg[5 * a.B * 8 + bid * 8 + (k)] = (int64_t)__builtin_amdgcn_s_memtime(); \
   } while (0)
+// The ring's barrier in front of a tap group: this wave's own DMAs of the group have landed once at
+// most N younger ones (the groups requested after it) are in flight, its reads of the retiring group
+// have returned (lgkmcnt), and the barrier then says both of every wave. LDS-DMA is invisible to the
+// compiler's wait insertion and __syncthreads() would wait for every DMA in flight (vmcnt(0)), the
+// look-ahead included; the memory clobber keeps fragment reads and DMAs on their side of it.
+#define C2D_PUB(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+__device__ __forceinline__ void c2d_publish(int n) {
+  switch (n) {
+    C2D_PUB(1) C2D_PUB(2) C2D_PUB(3) C2D_PUB(4) C2D_PUB(5) C2D_PUB(6) C2D_PUB(7) C2D_PUB(8) C2D_PUB(9) C2D_PUB(10)
+    default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+}
+template <int TPS, int RING>
 __device__ __forceinline__ void conv2_dgrad_body(const MnistStepArgs& a, const int bid) {
+  constexpr int NGR = (25 + TPS - 1) / TPS, AHEAD = RING / TPS;  // tap groups; groups the ring holds
+  static_assert(RING % TPS == 0 && (AHEAD >= 2 || NGR == 1), "the ring holds whole groups, one in use and one in flight");
+  static_assert(!TFD_STAMP || 2 * (NGR - 1) <= 16, "ring stamps per block");
   C2D_STAMP(0);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   bf16* img = (bf16*)smem_raw;                           // [8][224][8]
-  bf16* wt = img + 8 * C2D_PLANE * 8;                    // ring: stage s in [s & 1] of [2][C2D_TPS * 32][64]
+  bf16* wt = img + 8 * C2D_PLANE * 8;                    // ring: tap T in slot T % RING of [RING][32][64]
   const int b = bid >> 1, h = bid & 1, t = threadIdx.x;
   const uint16_t* src = a.dz2 + (size_t)b * 196 * 64;
   const uint16_t* wsrc = a.pbf + OFF_WC2;
   // the tail's x image row: its loads go out before the staging, whose wait then covers them (as a
   // chain issued after the staging, two dependent round trips held the waves at the next barrier)
   const RowPre xr = data_row_pre(a, b);
-  // W2 stage st (taps [st * C2D_TPS, +C2D_TPS): rows tap * 32 + ci) -> ring slot st & 1 by LDS-DMA
-  // (global_load_lds_dwordx4: no VGPR round trip, no ds_write pass; one wave instruction = 8 rows)
-  auto wdma = [&](int st) {
-    constexpr int NI = C2D_WSTAGE / 512;  // wave instructions per stage
-    static_assert(NI % (C2B_NT / 64) == 0, "whole DMA instructions per wave");
-    const int wv = t >> 6, ln = t & 63;
-    const uint16_t* s0 = wsrc + st * C2D_WSTAGE;
-    bf16* d0 = wt + (st & 1) * C2D_WSTAGE;
+  // W2 group gr (taps [gr * TPS, +TPS) below 25: rows tap * 32 + ci) -> the taps' ring slots by LDS-DMA
+  // (global_load_lds_dwordx4: no VGPR round trip, no ds_write pass; one wave instruction = 8 rows, so
+  // every wave issues exactly ONE instruction per tap -- what c2d_publish's counts are made of)
+  static_assert(C2D_WTAP / 512 == C2B_NT / 64, "one DMA instruction per wave and tap");
+  auto wdma = [&](int gr) {
+    const int p = t, rr = p >> 3, sl = p & 7;  // wave w: rows 8 w .. 8 w + 7 of the tap
 #pragma unroll
-    for (int k = 0; k < NI / (C2B_NT / 64); ++k) {
-      const int ii = wv + (C2B_NT / 64) * k, p = ii * 64 + ln, rr = p >> 3, sl = p & 7;
-      __builtin_amdgcn_global_load_lds((const void*)(s0 + rr * 64 + ((sl ^ (rr & 7)) << 3)),
-                                       (__attribute__((address_space(3))) void*)(d0 + ii * 64 * 8), 16, 0, 0);
-    }
+    for (int tap = gr * TPS; tap < gr * TPS + TPS && tap < 25; ++tap)
+      __builtin_amdgcn_global_load_lds((const void*)(wsrc + tap * C2D_WTAP + rr * 64 + ((sl ^ (rr & 7)) << 3)),
+                                       (__attribute__((address_space(3))) void*)(wt + (tap % RING) * C2D_WTAP + (t >> 6) * 512),
+                                       16, 0, 0);
   };
   {
     constexpr int CI = 8 * C2D_PLANE, NI = CI / C2B_NT;  // 1792 chunks -> 7 per thread
     static_assert(CI % C2B_NT == 0, "whole image chunks per thread");
-    wdma(0);  // the first two stages of the ring: in flight with the image staging
-    wdma(1);
+#pragma unroll
+    for (int gr = 0; gr < AHEAD && gr < NGR; ++gr) wdma(gr);  // the whole ring: in flight with the image staging
     uint4 vi[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
@@ -1112,22 +1134,35 @@ __device__ __forceinline__ void conv2_dgrad_body(const MnistStepArgs& a, const i
     bf16x8 fb[2][2], fa[2][2];
     auto ld = [&](int st, int slot) {
       const int tap = st >> 1, sk = st & 1;
-      const int woff = ((tap / C2D_TPS) & 1) * C2D_WSTAGE + (tap % C2D_TPS) * 32 * 64;
+      const int woff = (tap % RING) * C2D_WTAP;
       const int kh = tap / 5, kw = tap - kh * 5, aoff = ((4 - kh) * C2D_COLS + 4 - kw) * 8 + sk * 4 * C2D_PLANE * 8;
       fb[slot][0] = *reinterpret_cast<const bf16x8*>(bw[sk][0] + woff);
       fb[slot][1] = *reinterpret_cast<const bf16x8*>(bw[sk][1] + woff);
       fa[slot][0] = *reinterpret_cast<const bf16x8*>(a0 + aoff);
       fa[slot][1] = *reinterpret_cast<const bf16x8*>(a1 + aoff);
     };
-    constexpr int NS = 50, SPS = 2 * C2D_TPS;  // steps, steps per W2 stage
+    // Ring invariant. Group g's DMAs are issued (up front for g < AHEAD, else behind the barrier in front
+    // of group g - AHEAD + 1) in group order, one instruction per wave and tap, and a wave's DMAs retire
+    // in issue order. In front of group g the groups g + 1 .. g + AHEAD - 2 are the only younger ones:
+    // vmcnt(their tap count) means this wave's part of g has landed, the barrier that every wave's has,
+    // before any fragment read of g (all issued behind it). Every fragment read of group g - 1 is issued
+    // before that barrier and has returned (lgkmcnt(0)), and only behind it do DMAs go into g - 1's slots.
+    constexpr int NS = 50, SPS = 2 * TPS;  // steps, steps per W2 group
+    int64_t ts[2 * NGR];
     ld(0, 0);
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
       const int cur = st & 1;
       if (st + 1 < NS) {
         if ((st + 1) % SPS == 0) {
-          __syncthreads();
-          if ((st + 1) / SPS + 1 < C2D_NST) wdma((st + 1) / SPS + 1);
+          const int gr = (st + 1) / SPS;
+          int young = 0;
+#pragma unroll
+          for (int q = gr + 1; q <= gr + AHEAD - 2 && q < NGR; ++q) young += min(TPS, 25 - q * TPS);
+          if (TFD_STAMP) ts[2 * gr - 2] = (int64_t)__builtin_amdgcn_s_memtime();
+          c2d_publish(young);
+          if (TFD_STAMP) ts[2 * gr - 1] = (int64_t)__builtin_amdgcn_s_memtime();
+          if (gr + AHEAD - 1 < NGR) wdma(gr + AHEAD - 1);
         }
         ld(st + 1, cur ^ 1);
       }
@@ -1137,6 +1172,11 @@ __device__ __forceinline__ void conv2_dgrad_body(const MnistStepArgs& a, const i
         acc[j][1] = mfma16x16x32(fa[cur][j], fb[cur][1], acc[j][1]);
       }
     }
+    // stamp builds: the clocks in front of and behind each ring barrier (group g = 1 ..: [2 g - 2],
+    // [2 g - 1]) into dbg[10 * B * 8 + bid * 16 + k], stored here so that no store sits among the DMAs
+    if (TFD_STAMP && a.dbg && t == 0)
+#pragma unroll
+      for (int k = 0; k < 2 * (NGR - 1); ++k) a.dbg[10 * a.B * 8 + bid * 16 + k] = ts[k];
   }
   // pinned here: wave 3 uses its second M-tile only under a branch (two), and the compiler sank that
   // tile's 100 MFMAs into it, keeping every step's fragments alive across the loop (400+ spills)
@@ -1389,7 +1429,18 @@ __global__ __launch_bounds__(C2B_NT, 2) void conv2_bwd_lds(C2B_HOT(HOT_PARAM) in
   if ((int)blockIdx.x < nw) {
     conv2_wgrad_body(a, blockIdx.x);
   } else {
-    conv2_dgrad_body(a, blockIdx.x - nw);
+    conv2_dgrad_body<C2D_TPS, C2D_RING>(a, blockIdx.x - nw);
+  }
+}
+// The same launch with all of W2 resident (131 KB, one block per CU, no ring to go wrong): the
+// reference of tests/test_conv2_dgrad_ring_gpu.py (mnist_backward_b(.., resident_w2 = true)); no step runs it.
+__global__ __launch_bounds__(C2B_NT, 2) void conv2_bwd_resident(C2B_HOT(HOT_PARAM) int nw, MnistStepArgs a_) {
+  MnistStepArgs a = a_;
+  C2B_HOT(HOT_SET)
+  if ((int)blockIdx.x < nw) {
+    conv2_wgrad_body(a, blockIdx.x);
+  } else {
+    conv2_dgrad_body<25, 25>(a, blockIdx.x - nw);
   }
 }
 
@@ -1535,12 +1586,18 @@ void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part) {
   TFD_LAUNCH(fc1_bwd<<<nb, 256, sm, s>>>(FC1B_HOT(HOT_PASS) n_dx, part, a));
 }
 
-void mnist_backward_b(const MnistStepArgs& a, hipStream_t s) {
+void mnist_backward_b(const MnistStepArgs& a, hipStream_t s, bool resident_w2) {
   // conv2 wgrad (one slab per image group), then dgrad + conv1 wgrad, in one launch (a forked wgrad
   // stream only contended with dgrad for the CUs: 110 vs 100 us/step, profiles/ab_conv_fork.log)
   static_assert(C2WL_SMEM <= C2D_SMEM, "conv2_bwd_lds: the dgrad LDS size covers the wgrad blocks");
-  set_smem<conv2_bwd_lds>(C2D_SMEM);
   const int nw = C2WL_NTG * a.wg2_splits;
+  if (resident_w2) {
+    static_assert(c2d_smem(25) <= 160 * 1024, "resident W2");
+    set_smem<conv2_bwd_resident>(c2d_smem(25));
+    TFD_LAUNCH(conv2_bwd_resident<<<nw + 2 * a.B, C2B_NT, c2d_smem(25), s>>>(C2B_HOT(HOT_PASS) nw, a));
+    return;
+  }
+  set_smem<conv2_bwd_lds>(C2D_SMEM);
   TFD_LAUNCH(conv2_bwd_lds<<<nw + 2 * a.B, C2B_NT, C2D_SMEM, s>>>(C2B_HOT(HOT_PASS) nw, a));
 }
 

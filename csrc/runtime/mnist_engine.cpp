@@ -567,6 +567,14 @@ class MnistEngine : public torch::CustomClassHolder {
     mnist_backward_b(a, stream());
     mnist_conv_grad_reduce(a, stream());
   }
+  // Debug op: the conv2 backward launch alone on a given dz2 (no slab reduce, no step bump), with the
+  // dgrad's W2 ring or with all of W2 resident in LDS; its slabs are conv_grad_slabs().
+  void conv2_bwd_debug(at::Tensor dz2, bool resident_w2) {
+    TORCH_CHECK(!fp32_ && dz2.scalar_type() == at::kBFloat16 && dz2.numel() == dz2_.numel(), "conv2_bwd_debug: bf16 dz2 [B,14,14,64]");
+    dz2_.copy_(dz2.view_as(dz2_));
+    mnist_backward_b(args(), stream(), resident_w2);
+  }
+  std::vector<at::Tensor> conv_grad_slabs() { return {wg1_slab_, wg2_slab_}; }
   void apply_optimizer(double grad_scale) {
     apply_optimizer_range(0, TOTAL, grad_scale, 0, stream());
   }
@@ -2111,6 +2119,8 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("forward", &MnistEngine::forward)
       .def("backward_a", &MnistEngine::backward_a)
       .def("backward_b", &MnistEngine::backward_b)
+      .def("conv2_bwd_debug", &MnistEngine::conv2_bwd_debug)
+      .def("conv_grad_slabs", &MnistEngine::conv_grad_slabs)
       .def("apply_optimizer", &MnistEngine::apply_optimizer)
       .def("reduce_grads", &MnistEngine::reduce_grads)
       .def("train_step", &MnistEngine::train_step)

@@ -83,7 +83,8 @@ void mnist_forward_nohead(const MnistStepArgs& a, hipStream_t s);
 // part 2: dX (DP launches 1 then 2 so bucket A's all-reduce starts before the dX GEMM)
 void mnist_backward_a(const MnistStepArgs& a, hipStream_t s, int part = 0);
 // conv2 wgrad slabs + conv2 dgrad + conv1 wgrad slabs (one launch) -> bucket B's slabs done
-void mnist_backward_b(const MnistStepArgs& a, hipStream_t s);
+// (resident_w2: the dgrad with all of W2 in LDS and no ring, one block per CU -- the tests' reference)
+void mnist_backward_b(const MnistStepArgs& a, hipStream_t s, bool resident_w2 = false);
 // deterministic conv weight-gradient slab reduction (+ the global_step bump, MnistStepArgs::step_bump)
 void mnist_conv_grad_reduce(const MnistStepArgs& a, hipStream_t s);
 

@@ -15,7 +15,7 @@ dev = torch.device("cuda", 0)
 B = 128
 eng = torch.classes.tfd.MnistEngine(B, 0, 0.75, 1, 0)
 eng.set_adam(0.01, 0.9, 0.999, 1e-8)
-dbg = torch.zeros(10 * B * 8, dtype=torch.int64, device=dev)
+dbg = torch.zeros(14 * B * 8, dtype=torch.int64, device=dev)  # [10 B * 8, +2 B * 16): the dgrad ring's barrier clocks
 eng.set_debug_buffer(dbg)
 s = torch.cuda.Stream()
 with torch.cuda.stream(s):
@@ -78,7 +78,21 @@ if (dg[:, 7] > 0).all():
         dd = dg[:, k + 1] - dg[:, k]
         print(f"dgrad {dn[k]:28s} median {dd.median().item():8d}  p90 {dd.float().quantile(0.9).item():8.0f}")
 
-wg = dbg.view(-1, 8).cpu()[7 * B:9 * B]
+    # The W2 ring, per tap group: the clocks in front of and behind the barrier that publishes the group
+    # (its DMA wait + the barrier) and the group's MFMA phase up to the next barrier (or the loop's end).
+    rg = dbg.cpu()[10 * B * 8:14 * B * 8].view(2 * B, 16)
+    nb = int((rg[0] > 0).sum().item()) // 2  # ring barriers of this build
+    if nb:
+        def stat(name, dd):
+            print(f"dgrad ring {name:22s} median {dd.median().item():8d}  worst {dd.max().item():8d}")
+        stat("group 0 MFMA phase", rg[:, 0] - dg[:, 2])
+        for g in range(1, nb + 1):
+            stat(f"group {g} wait+barrier", rg[:, 2 * g - 1] - rg[:, 2 * g - 2])
+            stat(f"group {g} MFMA phase", (rg[:, 2 * g] if g < nb else dg[:, 3]) - rg[:, 2 * g - 1])
+        waits = sum(rg[:, 2 * g - 1] - rg[:, 2 * g - 2] for g in range(1, nb + 1))
+        stat("sum of waits", waits)
+
+wg = dbg.view(-1, 8).cpu()[7 * B:7 * B + 6 * (B // 4)]  # the wgrad blocks: 6 tap groups x B / 4 image groups
 if (wg[:, 7] > 0).all():
     wn2 = ["zero + image 0 loads + LDS stores + barrier", "image 0 MFMAs", "image 1 LDS stores + barrier",
            "image 1 MFMAs"]
@@ -88,3 +102,5 @@ if (wg[:, 7] > 0).all():
         print(f"wgrad {wn2[k]:44s} median {dd.median().item():8d}  p90 {dd.float().quantile(0.9).item():8.0f}")
     dd = wg[:, 7] - wg[:, 4]
     print(f"wgrad {'slab epilogue (+ bias sum)':44s} median {dd.median().item():8d}")
+    if (dg[:, 7] > 0).all():  # which role ends the launch (as far as the XCDs' clocks agree)
+        print("last wgrad end - last dgrad end:", (wg[:, 7].max() - dg[:, 7].max()).item(), "cycles")
