@@ -22,6 +22,7 @@
 #include "../ema.h"
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
+#include "../mnist_augment.h"
 #include "../mnist_infer.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
@@ -205,8 +206,42 @@ class MnistEngine : public torch::CustomClassHolder {
   // mode 0 = feed buffers (feed_x/feed_y filled by the host each step), 1 = device dataset + perm
   void set_input_mode(int64_t mode) {
     TORCH_CHECK(mode == 0 || (mode == 1 && data_.defined()), "set_dataset first");
+    TORCH_CHECK(mode == 1 || !aug_on_, "set_input_mode(0): augmentation warps rows of the device dataset; set_augment(0, 0, 0, 0, 0) first");
     input_mode_ = mode;
   }
+  // Train-time augmentation on the device (csrc/mnist_augment.h): random shifts of up to shift_px pixels,
+  // rotations of up to rotate_deg degrees, scales in [1 - scale, 1 + scale] and elastic distortion (alpha,
+  // sigma in pixels). While any magnitude is non-zero every training step body starts with one launch that
+  // warps its (micro-)batch -- the rows the device cursor selects from the dataset -- into a feed-mode pair,
+  // and the step kernels read that pair as fed rows: same kernels, same arguments but the batch pointers, no
+  // prefetch gather. The draws are a function of (seed, rank, sample number), so eager steps, replays, n-step
+  // graphs and micro-batches agree. evaluate / predict / evaluate_dataset / capture_eval never augment. All
+  // zeros (the default) is off: the step is launch for launch what it was. Needs the device dataset
+  // (set_input_mode(1)). Baked into graphs: a call that changes the config drops them.
+  void set_augment(double shift_px, double rotate_deg, double scale, double elastic_alpha, double elastic_sigma) {
+    AugmentConfig c;
+    try {
+      c = make_augment_config(shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma);
+    } catch (const std::invalid_argument& e) {
+      TORCH_CHECK(false, e.what());
+    }
+    const bool on = augment_on(c);
+    TORCH_CHECK(!on || input_mode_ == 1, "set_augment: augmentation warps rows of the device dataset: set_dataset and "
+                "set_input_mode(1) first");
+    const std::vector<double> user = {shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma};
+    if (user == aug_user_) return;
+    for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
+    graphs_.clear();
+    if (on && !xaug_.defined()) {
+      xaug_ = at::zeros({B_, 784}, xbuf_.options());
+      yaug_ = at::zeros({B_}, ybuf_.options());
+    }
+    aug_ = c;
+    aug_on_ = on;
+    aug_user_ = user;
+  }
+  // {shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma} in use (all zeros: off)
+  std::vector<double> augment() const { return aug_user_; }
   void set_keep_prob(double kp) { keep_prob_ = kp; }
   void sync_shadow() {
     cast_f32_bf16((const float*)params_.data_ptr(), (uint16_t*)pbf_.data_ptr(), TOTAL, stream());
@@ -545,6 +580,7 @@ class MnistEngine : public torch::CustomClassHolder {
 
   // ---- step pieces (current HIP stream) ----
   void forward(bool train) {
+    if (train) augment_head((const int64_t*)step_.data_ptr(), stream());
     if (fp32_) mnist_f32_forward(args_f32(), train, stream());
     else mnist_forward(args(), train, stream());
   }
@@ -661,6 +697,7 @@ class MnistEngine : public torch::CustomClassHolder {
       return;
     }
     mark(P_START, s);
+    augment_head((const int64_t*)step_.data_ptr(), s);
     MnistStepArgs a = args();
     // one GPU: nothing to overlap with. With Adam ONE kernel ends the step: it reduces the conv
     // weight-gradient slabs itself and bumps the step (its t was written by the head kernel).
@@ -716,6 +753,7 @@ class MnistEngine : public torch::CustomClassHolder {
     MnistStepArgs a = args();
     set_dp_outputs(a, bf);
     mark(P_START, s);
+    augment_head(a.step, s);
     mnist_forward_conv(a, s);
     tag("conv_fwd", s);
     if (pending_opt_a_) {
@@ -776,6 +814,7 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     set_dp_outputs(a, bf);
     mark(P_START, s);
+    augment_head(a.step, s);
     // last step's fc1 bf16 shards -> every rank, beside the conv fwd
     if (shard && pending_wag_ && !wag_issued_) gather_weights(s, "wag<-opt");
     mnist_forward_conv(a, s);
@@ -881,6 +920,7 @@ class MnistEngine : public torch::CustomClassHolder {
     const bool fused = !dp && opt_ == OptKind::Adam && fuse_tail_;
     if (fused) f.t_out = (int64_t*)tnext_.data_ptr();
     mark(P_START, s);
+    augment_head(f.step, s);
     mnist_f32_forward(f, true, s);
     log_loss(f.step, SL_WHOLE, s);
     mark(P_FWD, s);
@@ -929,6 +969,7 @@ class MnistEngine : public torch::CustomClassHolder {
       pending_opt_a_ = false;
     }
     mark(P_START, s);
+    augment_head(step, s);
     MnistStepArgs a = args();
     if (fp32_) {
       MnistF32Args f = args_f32();
@@ -1044,6 +1085,7 @@ class MnistEngine : public torch::CustomClassHolder {
         a.data += j * B_ * 784;
         a.labels += j * B_;
       }
+      augment_head(micro, s);
       if (fp32_) {
         MnistF32Args f = args_f32(a);
         mnist_f32_forward(f, true, s);
@@ -1107,6 +1149,7 @@ class MnistEngine : public torch::CustomClassHolder {
     const double scale = 1.0 / (double)world();
     const int64_t r = rank_in_comm();
     MnistStepArgs a = args();
+    augment_head(a.step, s);
     // all-gather last step's updated fc1 shadow shards, overlapping the conv forward
     hand_off(s, ev_start_, comm_stream_, "zero:wag<-prev_opt");
     ag_w(comm_stream_);
@@ -1522,6 +1565,26 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("step_log_norm", s);
   }
 
+  // ---- device augmentation (set_augment): the one launch at the head of a training step body, on the
+  // body's main stream; cursor: what the body's kernels read as their data cursor. A no-op while off.
+  void augment_head(const int64_t* cursor, hipStream_t s) {
+    if (!aug_on_) return;
+    AugmentArgs g{};
+    g.data = (const float*)data_.data_ptr();
+    g.labels = (const int*)labels_.data_ptr();
+    g.perm = (const int*)perm_.data_ptr();
+    g.step = cursor;
+    g.n = (int)data_.size(0);
+    g.B = (int)B_;
+    g.seed = seed_;
+    g.rank = rank_;
+    g.xaug = (float*)xaug_.data_ptr();
+    g.yaug = (int*)yaug_.data_ptr();
+    g.cfg = aug_;
+    tfd::augment_batch(g, s);
+    tag("augment", s);
+  }
+
   // ---- argument structs of the optimizer kernels: each is filled in one place ----
   // Range [beg, beg + n) of the flat buffers; bf_grads: the gradients are bf16 in gbf_
   AdamArgs adam_args(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t) {
@@ -1880,7 +1943,14 @@ class MnistEngine : public torch::CustomClassHolder {
   MnistStepArgs args() {
     MnistStepArgs a{};
     a.B = (int)B_;
-    if (input_mode_ == 1) {
+    // augmentation: the step reads the warped pair as fed rows (no perm, no prefetch)
+    const bool gather = input_mode_ == 1 && !aug_on_;
+    if (aug_on_) {
+      a.data = (const float*)xaug_.data_ptr();
+      a.labels = (const int*)yaug_.data_ptr();
+      a.perm = nullptr;
+      a.n_data = (int)B_;
+    } else if (input_mode_ == 1) {
       a.data = (const float*)data_.data_ptr();
       a.labels = (const int*)labels_.data_ptr();
       a.perm = (const int*)perm_.data_ptr();
@@ -1913,9 +1983,9 @@ class MnistEngine : public torch::CustomClassHolder {
     a.keep_prob = (float)keep_prob_;
     a.seed = seed_;
     a.rank = rank_;
-    a.rows = input_mode_ == 1 ? (int*)rows_.data_ptr() : nullptr;
-    a.xpre = input_mode_ == 1 ? (float*)xpre_.data_ptr() : nullptr;
-    a.ypre = input_mode_ == 1 ? (int*)ypre_.data_ptr() : nullptr;
+    a.rows = gather ? (int*)rows_.data_ptr() : nullptr;
+    a.xpre = gather ? (float*)xpre_.data_ptr() : nullptr;
+    a.ypre = gather ? (int*)ypre_.data_ptr() : nullptr;
     a.dbg = dbg_.defined() ? (int64_t*)dbg_.data_ptr() : nullptr;
     if (sfb_active()) {
       const int64_t r = rank_in_comm();
@@ -1960,6 +2030,12 @@ class MnistEngine : public torch::CustomClassHolder {
   at::Tensor p1_, idx1_, p2_, idx2_, fc1_slab_, hd_, dh_, dlogits_, loss_row_, correct_row_, dz2_, wg2_slab_,
       wg1_slab_, xbuf_, ybuf_;
   at::Tensor data_, labels_, perm_, rows_, xpre_, ypre_, dbg_;
+  // device augmentation (set_augment): the config, whether any magnitude is non-zero, the caller's five
+  // numbers, and the warped batch the step kernels read as fed rows
+  AugmentConfig aug_{};
+  bool aug_on_ = false;
+  std::vector<double> aug_user_ = std::vector<double>(5, 0.0);
+  at::Tensor xaug_, yaug_;
   at::Tensor f1_, f2_, fhd_, fdh_, fdz2_, fslab_, fwg2_;  // fp32-mode activations / slabs
   bool fp32_ = false;
   HipStream comm_stream_;
@@ -2069,6 +2145,8 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("invalidate_prefetch", &MnistEngine::invalidate_prefetch)
       .def("set_debug_buffer", &MnistEngine::set_debug_buffer)
       .def("set_input_mode", &MnistEngine::set_input_mode)
+      .def("set_augment", &MnistEngine::set_augment)
+      .def("augment", &MnistEngine::augment)
       .def("set_keep_prob", &MnistEngine::set_keep_prob)
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -21,6 +21,7 @@ import torch  # noqa: E402
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
 from tensorflow_distributed_amd.training import checkpoint, inference  # noqa: E402
+from tensorflow_distributed_amd.training.augment import augment_config, augment_on  # noqa: E402
 from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
 from tensorflow_distributed_amd.training.optimizers import (AdagradOptimizer, AdamOptimizer, LAMBOptimizer,  # noqa: E402
                                                             LARSOptimizer, RMSPropOptimizer)
@@ -86,6 +87,14 @@ def main(argv=None):
                     "round trip. N > 1 replays N steps as one captured graph and reads their losses once per call from "
                     "the device step log; a call also ends at every --display_step multiple (the minibatch-loss forward "
                     "needs the last batch). GPU with the device-resident split only; 1 = one step per call")
+    ap.add_argument("--augment_shift", type=float, default=0.0, help="train-time augmentation: random shift of up to "
+                    "this many pixels per axis (GPU: warped on the device at the head of every step, inside the step "
+                    "graph; CPU: the same definition in numpy); the Minibatch Loss prints read the unwarped rows")
+    ap.add_argument("--augment_rotate", type=float, default=0.0, help="augmentation: random rotation, degrees")
+    ap.add_argument("--augment_scale", type=float, default=0.0, help="augmentation: random scale in [1 - s, 1 + s]")
+    ap.add_argument("--elastic_alpha", type=float, default=0.0, help="augmentation: elastic distortion, displacement "
+                    "scale in pixels (Simard et al.: 34 with sigma 4)")
+    ap.add_argument("--elastic_sigma", type=float, default=0.0, help="--elastic_alpha: the Gaussian's sigma in pixels")
     ap.add_argument("--device_eval", action="store_true", help="upload the validation split once and evaluate it on "
                     "the device: the --eval_batches x 100 rows in split order (not next_batch's shuffle: the same mean "
                     "whenever they are the whole split, as the default 50 x 100 are), one record per batch folded by the "
@@ -110,6 +119,14 @@ def main(argv=None):
             ap.error("--steps_per_call > 1 with --no_graph: the steps of a call are one captured graph")
     if a.confusion_matrix and not a.device_eval:
         ap.error("--confusion_matrix is folded by --device_eval: give both")
+    augment = (a.augment_shift, a.augment_rotate, a.augment_scale, a.elastic_alpha, a.elastic_sigma)
+    try:
+        augment_config(*augment)
+    except ValueError as e:
+        ap.error(str(e))
+    if augment_on(augment_config(*augment)) and a.host_feed and not a.cpu and torch.cuda.is_available():
+        ap.error("--augment_* / --elastic_* with --host_feed: the device kernel warps rows of the device-resident "
+                 "split; a host-fed GPU run has none")
     step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
@@ -144,6 +161,8 @@ def main(argv=None):
     device_input = dev.type == "cuda" and not a.host_feed
     if device_input:  # upload the split once; batches are gathered on the GPU (no per-step feed)
         runner.set_device_dataset(mnist.train.images, mnist.train.labels, seed=a.seed + 101)
+    if augment_on(augment_config(*augment)):
+        runner.set_augment(*augment)
 
     start_time = time.time()
     train_flag = a.train_flag

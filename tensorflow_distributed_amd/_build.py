@@ -36,7 +36,8 @@ ARCH = os.environ.get("TFD_OFFLOAD_ARCH", "gfx950")
 # argument segment in front of it. Per file: every other code object stays byte for byte what it was.
 # tools/isa_waits.py mirrors the flags and the list.
 PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
-PRELOAD_SOURCES = ("mnist.hip", "mnist_tail_sched.hip", "mnist_tail_ema.hip", "kernarg_probe.hip")
+PRELOAD_SOURCES = ("mnist.hip", "mnist_tail_sched.hip", "mnist_tail_ema.hip", "kernarg_probe.hip",
+                   "mnist_augment.hip")
 
 
 def _torch_dirs():

@@ -224,6 +224,8 @@ class TorchMnistRunner(MnistRunnerBase):
         self._log_cap = 0   # step log (set_step_log): capacity, 0 = off
         self._log = {}      # slot -> record
         self._log_sums = []  # (loss sum, correct, rows) of the current step's micro-batches
+        self._seed, self._rank = int(seed), int(rank)
+        self._aug = None    # augmentation config (set_augment), None = off
 
     def params(self) -> torch.Tensor:
         return self.flat
@@ -311,6 +313,8 @@ class TorchMnistRunner(MnistRunnerBase):
         applied once at scale ``1 / accum_steps``. The loss is the last micro-batch's."""
         K, B = self.accum_steps, self.batch_size
         self._log_sums = []
+        if self._aug is not None:
+            x = self._augmented(x)
         if K == 1:
             g, _ = self.compute_grads(x, y)
             if self.comm is not None:
@@ -329,6 +333,22 @@ class TorchMnistRunner(MnistRunnerBase):
             self.comm(self.grad)
         self.apply_grads(self.grad, 1.0 / K)
         self._log_step()
+
+    # ---- data augmentation: the device kernel's fp64 reference on every training batch ----
+    def set_augment(self, shift_px=0.0, rotate_deg=0.0, scale=0.0, elastic_alpha=0.0, elastic_sigma=0.0) -> None:
+        """Warp every ``train_step``'s rows with ``training.augment``'s reference; row ``b`` of the step
+        at ``global_step = t`` is sample ``t * rows + b``, the device's numbering. All zeros turns it off."""
+        from ..training.augment import augment_config, augment_on
+
+        cfg = augment_config(shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma)
+        self._aug = cfg if augment_on(cfg) else None
+
+    def _augmented(self, x) -> torch.Tensor:
+        from ..training.augment import native_augment_draws, warp_rows_ref
+
+        x = _as_f32(x)
+        draws = native_augment_draws(x.shape[0], self._step, self._rank, self._seed)
+        return torch.from_numpy(warp_rows_ref(x.cpu().numpy(), self._aug, draws)).float()
 
     # ---- step log: the device runner's three methods over a plain Python ring ----
     def set_step_log(self, capacity: int = 1024) -> None:
@@ -557,6 +577,22 @@ class NativeMnistRunner(MnistRunnerBase):
             self.eng.set_step_log(int(capacity))
         self._stale_graphs()
         self._grads_graph = False
+
+    # ---- device data augmentation (csrc/mnist_augment.h) ----
+    def set_augment(self, shift_px=0.0, rotate_deg=0.0, scale=0.0, elastic_alpha=0.0, elastic_sigma=0.0) -> None:
+        """Warp every training (micro-)batch on the device at the head of its step body -- random shift,
+        rotation, scale and elastic distortion, drawn from (seed, rank, sample number) -- so device input,
+        ``steps_per_call`` graphs and evaluation stay what they are. All zeros turns it off. Needs
+        ``set_device_dataset`` first; the captured graphs are dropped."""
+        self.stream.synchronize()  # the engine drops its graphs: none may still be running
+        with torch.cuda.stream(self.stream):
+            self.eng.set_augment(float(shift_px), float(rotate_deg), float(scale), float(elastic_alpha),
+                                 float(elastic_sigma))
+        self._stale_graphs()
+        self._grads_graph = False
+
+    def augment(self) -> dict:
+        return dict(zip(("shift", "rotate", "scale", "elastic_alpha", "elastic_sigma"), self.eng.augment()))
 
     def read_step_log(self, first_t: int, last_t: int) -> list:
         """The records of optimizer steps ``first_t..last_t`` (``t`` = global_step after the step) as dicts

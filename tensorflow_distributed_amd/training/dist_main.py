@@ -201,6 +201,14 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "CPU ps (ps_device=/job:ps/cpu:0)")
     f.DEFINE_boolean("device_input", True, "GPU: upload the training split once and index it on the device "
                      "by a per-epoch shuffle (no per-step host feed); False = host next_batch + H2D per step")
+    f.DEFINE_float("augment_shift", 0.0, "Train-time augmentation (--model mnist_cnn, one worker or synchronous all-reduce "
+                   "DP): random shift of up to this many pixels per axis. GPU: every (micro-)batch is warped on the device "
+                   "at the head of its step body, inside the step graph (csrc/mnist_augment.h), from draws keyed by "
+                   "(seed, worker, sample number); CPU: the same definition in numpy (training/augment.py). 0 = off")
+    f.DEFINE_float("augment_rotate", 0.0, "Augmentation: random rotation of up to this many degrees")
+    f.DEFINE_float("augment_scale", 0.0, "Augmentation: random scale in [1 - s, 1 + s], s < 1")
+    f.DEFINE_float("elastic_alpha", 0.0, "Augmentation: elastic distortion (Simard et al.), displacement scale in pixels")
+    f.DEFINE_float("elastic_sigma", 0.0, "--elastic_alpha: sigma of the Gaussian that smooths the displacement field, pixels")
 
 
 def _make_learning_rate():
@@ -365,6 +373,32 @@ def check_skip_nonfinite_flags(num_workers: int) -> None:
         raise ValueError("--skip_nonfinite with --dp_schedule=%s: the guard reads the whole aggregated gradient on "
                          "every rank, which the SFB / ZeRO schedules never form; use the all-reduce schedule"
                          % FLAGS.dp_schedule)
+
+
+def augment_flags() -> tuple:
+    """(shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma) of the --augment_* / --elastic_* flags"""
+    return (FLAGS.augment_shift, FLAGS.augment_rotate, FLAGS.augment_scale, FLAGS.elastic_alpha, FLAGS.elastic_sigma)
+
+
+def check_augment_flags(num_workers: int) -> bool:
+    """Whether the --augment_* / --elastic_* flags turn augmentation on. What it does not cover is a flag error,
+    raised before any process group is built (every rank sees the same flags)."""
+    from .augment import augment_config, augment_on
+
+    if not augment_on(augment_config(*augment_flags())):  # a bad magnitude raises here
+        return False
+    which = "--augment_* / --elastic_*"
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts)):
+        raise ValueError("%s with a parameter-server mode (%s): the worker's step there is a bare forward and backward "
+                         "on fed rows; augmentation belongs to the engine's training step"
+                         % (which, "--sync_replicas=False" if not FLAGS.sync_replicas else "backup workers"))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the warp is defined on 28 x 28 MNIST rows" % (which, FLAGS.model))
+    if FLAGS.num_gpus > 0 and not FLAGS.device_input:
+        raise ValueError("%s with --device_input=False: the device kernel warps rows of the device-resident split; a "
+                         "host-fed GPU run has none" % which)
+    return True
 
 
 def check_steps_per_call_flags(num_workers: int) -> None:
@@ -854,6 +888,7 @@ def main(argv=None) -> int:
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
     check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))
+    check_augment_flags(len(FLAGS.worker_hosts.split(",")))
     check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
@@ -942,6 +977,12 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     if device_input:
         runner.set_device_dataset(mnist.train.images, mnist.train.labels,
                                   seed=FLAGS.seed * 1000 + FLAGS.task_index + 31)
+    augment = check_augment_flags(num_workers)
+    if augment:
+        if device.type == "cuda" and not device_input:
+            raise ValueError("--augment_* / --elastic_*: %s feeds the GPU engine from the host; the device kernel "
+                             "warps rows of the device-resident split" % gsync.describe())
+        runner.set_augment(*augment_flags())
 
     sv = _prepare_session(cluster, is_chief, runner,
                           lambda: runner.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0), gsync.broadcast)
@@ -1070,6 +1111,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                     rec["skipped_steps"], rec["step_ok"] = skipped, r["ok"]
                 if opt.ema_decay:
                     rec["ema_decay"] = ema_decay_at(opt.ema_decay, r["step"], opt.ema_num_updates)
+                if augment:
+                    rec["augment"] = list(augment_flags())
                 if last and phase_timing:
                     ph = runner.phase_times()
                     rec.update(ph)
@@ -1111,6 +1154,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 rec["skipped_steps"], rec["step_ok"] = runner.skipped_steps(), runner.last_step_ok()
             if opt.ema_decay:  # d_t of this step's update (host mirror)
                 rec["ema_decay"] = ema_decay_at(opt.ema_decay, step, opt.ema_num_updates)
+            if augment:
+                rec["augment"] = list(augment_flags())
             if phase_timing:
                 ph = runner.phase_times()
                 rec.update(ph)

@@ -38,7 +38,8 @@ VLOAD = re.compile(r"^\s*(global_load|buffer_load)")
 # Kernel-argument preload (gfx950: leading pointer / scalar kernel parameters arrive in user SGPRs at
 # wave launch). Mirrors tensorflow_distributed_amd/_build.py: the same flags for the same files.
 PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
-PRELOAD_SOURCES = ("mnist.hip", "mnist_tail_sched.hip", "mnist_tail_ema.hip", "kernarg_probe.hip")
+PRELOAD_SOURCES = ("mnist.hip", "mnist_tail_sched.hip", "mnist_tail_ema.hip", "kernarg_probe.hip",
+                   "mnist_augment.hip")
 
 
 def flags_for(src):
