@@ -12,10 +12,12 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <cmath>
 #include <limits>
 #include <map>
 #include <set>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -23,6 +25,7 @@
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
 #include "../mnist_augment.h"
+#include "../mnist_input_grad.h"
 #include "../mnist_infer.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
@@ -134,6 +137,8 @@ class MnistEngine : public torch::CustomClassHolder {
   // pre-activation
   at::Tensor pool1_argmax() { return idx1_; }
   at::Tensor pool2_argmax() { return idx2_; }
+  // the dense conv2 pre-activation gradient [B,14,14,64] the fc1 data-gradient pass leaves (bf16 step)
+  at::Tensor conv2_preact_grad() { return dz2_; }
   at::Tensor dlogits() {
     if (!fp32_ && sfb_active())
       return sfdr_.narrow(0, rank_in_comm() * sfb_rs_ + 2 * B_ * HID, 2 * B_ * NCLS).view(at::kFloat).view({B_, NCLS});
@@ -162,6 +167,8 @@ class MnistEngine : public torch::CustomClassHolder {
   // at the buffers of the old K.
   void set_grad_accum(int64_t K) {
     TORCH_CHECK(K >= 1 && K <= 4096, "set_grad_accum: 1 <= K <= 4096, got ", K);
+    TORCH_CHECK(K == 1 || !adv_on_, "set_grad_accum(", K, ") with set_adversarial on: the adversarial pre-pass perturbs one "
+                "batch with one set of parameters, not K micro-batches; set_adversarial(0, -1) first");
     if (K != accum_) {
       for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
       graphs_.clear();
@@ -242,6 +249,121 @@ class MnistEngine : public torch::CustomClassHolder {
   }
   // {shift_px, rotate_deg, scale, elastic_alpha, elastic_sigma} in use (all zeros: off)
   std::vector<double> augment() const { return aug_user_; }
+
+  // ---- input gradient and FGSM (csrc/mnist_input_grad.h) ----
+  // The pass behind all three entry points, over nb <= B rows that `a` (args(true) with the caller's rows)
+  // names: the step's own forward in train mode at keep_prob = 1, the fc1 data gradient alone
+  // (mnist_backward_a part 2: it reads dh and the fc1 weights and writes dz2; no weight gradient, no
+  // collective), then input_grad_kernel. Nothing of the optimizer's is an output: t_out, step_bump, gbf_a and
+  // gbf_b are null. The head's loss and accuracy rows go to buffers of the pass's own, so loss_rows() and
+  // correct_rows() keep their bits; parameters, slots and counters are only read. The activations and
+  // gradients it does overwrite (p1 .. dz2, hidden, dlogits) are workspace every step rewrites whole.
+  void input_grad_pass(MnistStepArgs a, float eps, int adv_rows, float* dx, float* xadv, int* yadv, hipStream_t s) {
+    a.keep_prob = 1.0f;
+    a.t_out = nullptr;
+    a.step_bump = nullptr;
+    a.gbf_a = a.gbf_b = nullptr;
+    a.rows = nullptr;  // no prefetch: with the pre-pass on, no step gathers one
+    a.xpre = nullptr;
+    a.ypre = nullptr;
+    a.loss_row = (float*)adv_loss_.data_ptr();
+    a.correct_row = (float*)adv_correct_.data_ptr();
+    mnist_forward(a, true, s);
+    mnist_backward_a(a, s, 2);
+    InputGradArgs g{};
+    g.dz2 = a.dz2;
+    g.p1 = a.p1;
+    g.idx1 = a.idx1;
+    g.pbf = a.pbf;
+    g.data = a.data;
+    g.labels = a.labels;
+    g.perm = a.perm;
+    g.step = a.step;
+    g.n = a.n_data;
+    g.B = a.B;
+    g.eps = eps;
+    g.adv_rows = adv_rows;
+    g.dx = dx;
+    g.xadv = xadv;
+    g.yadv = yadv;
+    tfd::input_grad(g, s);
+  }
+  void adv_buffers() {
+    if (adv_loss_.defined()) return;
+    adv_loss_ = at::zeros({B_}, loss_row_.options());
+    adv_correct_ = at::zeros({B_}, loss_row_.options());
+    xadv_ = at::zeros({B_, 784}, xbuf_.options());
+    yadv_ = at::zeros({B_}, ybuf_.options());
+  }
+  // (dx, xadv) of fed rows x [n,784] fp32 / y [n] int32 in chunks of <= B rows; rows < adv_rows are perturbed.
+  // dx is the gradient of the MEAN loss over the chunk's rows (the reference's reduce_mean: the 1/rows the
+  // head folds into dlogits), at keep_prob = 1.
+  std::tuple<at::Tensor, at::Tensor> input_grad_rows(const char* who, at::Tensor x, at::Tensor y, double eps, int64_t adv_rows) {
+    TORCH_CHECK(!fp32_, who, ": not built for the fp32 engine (the kernel's operands are the bf16 step's); set_dtype('bf16')");
+    check_rows(who, x, at::kFloat, 2);
+    check_rows(who, y, at::kInt, 1);
+    const int64_t n = x.size(0);
+    TORCH_CHECK(x.size(1) == 784 && y.size(0) == n, who, ": x [n,784] fp32 and y [n] int32");
+    TORCH_CHECK(std::isfinite(eps) && eps >= 0, who, ": eps >= 0, got ", eps);
+    TORCH_CHECK(adv_rows >= -1 && adv_rows <= n, who, ": adv_rows in [0, n] or -1 (all), got ", adv_rows);
+    if (adv_rows < 0) adv_rows = n;
+    auto dx = at::empty({n, 784}, x.options());
+    auto xadv = at::empty({n, 784}, x.options());
+    auto yadv = at::empty({n}, y.options());
+    adv_buffers();
+    for (int64_t o = 0; o < n; o += B_) {
+      MnistStepArgs a = args(true);
+      a.B = (int)std::min<int64_t>(B_, n - o);
+      a.data = (const float*)x.data_ptr() + o * 784;
+      a.labels = (const int*)y.data_ptr() + o;
+      a.perm = nullptr;
+      a.n_data = a.B;
+      input_grad_pass(a, (float)eps, (int)std::max<int64_t>(0, std::min<int64_t>(a.B, adv_rows - o)),
+                      (float*)dx.data_ptr() + o * 784, (float*)xadv.data_ptr() + o * 784, (int*)yadv.data_ptr() + o, stream());
+    }
+    return {dx, xadv};
+  }
+  at::Tensor input_gradient(at::Tensor x, at::Tensor y) { return std::get<0>(input_grad_rows("input_gradient", x, y, 0.0, 0)); }
+  // xadv = clip(x + eps * sign(dL/dx), 0, 1) for rows < adv_rows (-1: all), the other rows copied
+  at::Tensor fgsm(at::Tensor x, at::Tensor y, double eps, int64_t adv_rows) {
+    return std::get<1>(input_grad_rows("fgsm", x, y, eps, adv_rows));
+  }
+  // FGSM adversarial training: while eps > 0 every training step body starts, right behind the augmentation
+  // launch, with the pass above over the rows the body would read (the augmented pair when set_augment is
+  // on), taken through the device cursor -- so an n-step graph perturbs each step's own rows with that
+  // step's parameters. It writes the feed-mode pair (xadv, yadv) and the body reads that pair as fed rows,
+  // with no prefetch gather: the dispatch in args() augmentation added. Rows >= adv_rows (-1: all B) stay
+  // clean. eps = 0 (the default) is off: the step is launch for launch what it was. Both input modes; one
+  // GPU and the all-reduce DP schedule (each rank perturbs its own rows). Baked into graphs: a change drops them.
+  void set_adversarial(double eps, int64_t adv_rows) {
+    TORCH_CHECK(std::isfinite(eps) && eps >= 0, "set_adversarial: eps >= 0, got ", eps);
+    TORCH_CHECK(adv_rows >= -1 && adv_rows <= B_, "set_adversarial: adv_rows in [0, B = ", B_, "] or -1 (all), got ", adv_rows);
+    const bool on = eps > 0;
+    if (on) {
+      TORCH_CHECK(!fp32_, "set_adversarial: not built for the fp32 engine (the input-gradient kernel reads the bf16 step's "
+                  "operands); set_dtype('bf16')");
+      TORCH_CHECK(accum_ == 1, "set_adversarial: gradient accumulation is on (grad_accum() = ", accum_, "): the pre-pass "
+                  "perturbs one batch with one set of parameters, not K micro-batches; set_grad_accum(1) first");
+      TORCH_CHECK(!sfb_active(), "set_adversarial: the sufficient-factor schedule (set_fc_sfb) keeps the fc factors in "
+                  "gathered slots the pre-pass would overwrite; use the all-reduce schedule");
+      TORCH_CHECK(!zero_, "set_adversarial: under ZeRO-1 (set_zero) the bf16 fc1 weights are whole only after the step's "
+                  "all-gather, behind the head of the body; use the all-reduce schedule");
+    }
+    const std::vector<double> user = {on ? eps : 0.0, (double)(on ? (adv_rows < 0 ? B_ : adv_rows) : -1)};
+    if (user == adv_user_) return;
+    for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
+    graphs_.clear();
+    adv_user_ = user;
+    adv_on_ = false;
+    invalidate_prefetch();  // no step gathers one while the pre-pass is on: a stale tag must not match later
+    if (!on) return;
+    adv_buffers();
+    // once outside any capture: the launchers raise their kernels' dynamic-LDS limits at their first launch
+    adv_on_ = true;
+    adversarial_head((const int64_t*)step_.data_ptr(), stream());
+  }
+  // {eps, adv_rows} in use ({0, -1}: off)
+  std::vector<double> adversarial() const { return adv_user_; }
   void set_keep_prob(double kp) { keep_prob_ = kp; }
   void sync_shadow() {
     cast_f32_bf16((const float*)params_.data_ptr(), (uint16_t*)pbf_.data_ptr(), TOTAL, stream());
@@ -484,6 +606,8 @@ class MnistEngine : public torch::CustomClassHolder {
   // matrix core (csrc/kernels/mnist_f32.hip); the gradient wire format becomes fp32 too.
   void set_dtype(const std::string& dt) {
     TORCH_CHECK(dt == "bf16" || dt == "fp32", "dtype must be bf16 or fp32");
+    TORCH_CHECK(dt == "bf16" || !adv_on_, "set_dtype('fp32') with set_adversarial on: the input-gradient kernel reads the "
+                "bf16 step's operands; set_adversarial(0, -1) first");
     const bool f = dt == "fp32";
     if (f && !f1_.defined()) {
       auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device_);
@@ -581,6 +705,7 @@ class MnistEngine : public torch::CustomClassHolder {
   // ---- step pieces (current HIP stream) ----
   void forward(bool train) {
     if (train) augment_head((const int64_t*)step_.data_ptr(), stream());
+    if (train) adversarial_head((const int64_t*)step_.data_ptr(), stream());
     if (fp32_) mnist_f32_forward(args_f32(), train, stream());
     else mnist_forward(args(), train, stream());
   }
@@ -668,6 +793,10 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(accum_ > 1 && (zero_ || sfb_active())), "set_grad_accum conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
                 ": the micro-batch gradients are summed whole before the one collective; use the all-reduce schedule");
+    // set_adversarial refuses these at set-up; they may have been switched on after it
+    TORCH_CHECK(!(adv_on_ && (zero_ || sfb_active())), "set_adversarial conflicts with ", zero_ ? "ZeRO-1 (set_zero)" :
+                "sufficient-factor fc gradients (set_fc_sfb)", ": the pre-pass needs whole parameters and buffers of its "
+                "own on every rank; use the all-reduce schedule");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -698,6 +827,7 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     mark(P_START, s);
     augment_head((const int64_t*)step_.data_ptr(), s);
+    adversarial_head((const int64_t*)step_.data_ptr(), s);
     MnistStepArgs a = args();
     // one GPU: nothing to overlap with. With Adam ONE kernel ends the step: it reduces the conv
     // weight-gradient slabs itself and bumps the step (its t was written by the head kernel).
@@ -754,6 +884,7 @@ class MnistEngine : public torch::CustomClassHolder {
     set_dp_outputs(a, bf);
     mark(P_START, s);
     augment_head(a.step, s);
+    adversarial_head(a.step, s);
     mnist_forward_conv(a, s);
     tag("conv_fwd", s);
     if (pending_opt_a_) {
@@ -970,6 +1101,7 @@ class MnistEngine : public torch::CustomClassHolder {
     }
     mark(P_START, s);
     augment_head(step, s);
+    adversarial_head(step, s);
     MnistStepArgs a = args();
     if (fp32_) {
       MnistF32Args f = args_f32();
@@ -1585,6 +1717,21 @@ class MnistEngine : public torch::CustomClassHolder {
     tag("augment", s);
   }
 
+  // ---- FGSM adversarial training (set_adversarial): the pre-pass at the head of a training step body, behind
+  // augment_head on the body's main stream; cursor as there. A no-op while off. In a DP graph the previous
+  // step's fc-region optimizer may still run on its own stream: the pre-pass reads the fc weights first.
+  void adversarial_head(const int64_t* cursor, hipStream_t s) {
+    if (!adv_on_) return;
+    if (pending_opt_a_) {
+      wait(s, ev_opt_a_, "adversarial<-opt_fc");
+      pending_opt_a_ = false;
+    }
+    MnistStepArgs a = args(true);
+    a.step = cursor;
+    input_grad_pass(a, (float)adv_user_[0], (int)adv_user_[1], nullptr, (float*)xadv_.data_ptr(), (int*)yadv_.data_ptr(), s);
+    tag("adversarial", s);
+  }
+
   // ---- argument structs of the optimizer kernels: each is filled in one place ----
   // Range [beg, beg + n) of the flat buffers; bf_grads: the gradients are bf16 in gbf_
   AdamArgs adam_args(int64_t beg, int64_t n, bool bf_grads, double grad_scale, int t_offset, const int64_t* t) {
@@ -1940,12 +2087,19 @@ class MnistEngine : public torch::CustomClassHolder {
     return f;
   }
 
-  MnistStepArgs args() {
+  // pre: the adversarial pre-pass's view, the rows the body would read without it
+  MnistStepArgs args(bool pre = false) {
     MnistStepArgs a{};
     a.B = (int)B_;
-    // augmentation: the step reads the warped pair as fed rows (no perm, no prefetch)
-    const bool gather = input_mode_ == 1 && !aug_on_;
-    if (aug_on_) {
+    // augmentation, adversarial training: the step reads the written pair as fed rows (no perm, no prefetch)
+    const bool adv = adv_on_ && !pre;
+    const bool gather = input_mode_ == 1 && !aug_on_ && !adv;
+    if (adv) {
+      a.data = (const float*)xadv_.data_ptr();
+      a.labels = (const int*)yadv_.data_ptr();
+      a.perm = nullptr;
+      a.n_data = (int)B_;
+    } else if (aug_on_) {
       a.data = (const float*)xaug_.data_ptr();
       a.labels = (const int*)yaug_.data_ptr();
       a.perm = nullptr;
@@ -2036,6 +2190,11 @@ class MnistEngine : public torch::CustomClassHolder {
   bool aug_on_ = false;
   std::vector<double> aug_user_ = std::vector<double>(5, 0.0);
   at::Tensor xaug_, yaug_;
+  // FGSM adversarial training (set_adversarial): on, {eps, adv_rows}, the perturbed batch the step kernels
+  // read as fed rows, and the loss / accuracy rows of the pre-pass's own head
+  bool adv_on_ = false;
+  std::vector<double> adv_user_ = {0.0, -1.0};
+  at::Tensor xadv_, yadv_, adv_loss_, adv_correct_;
   at::Tensor f1_, f2_, fhd_, fdh_, fdz2_, fslab_, fwg2_;  // fp32-mode activations / slabs
   bool fp32_ = false;
   HipStream comm_stream_;
@@ -2147,6 +2306,11 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("set_input_mode", &MnistEngine::set_input_mode)
       .def("set_augment", &MnistEngine::set_augment)
       .def("augment", &MnistEngine::augment)
+      .def("conv2_preact_grad", &MnistEngine::conv2_preact_grad)
+      .def("input_gradient", &MnistEngine::input_gradient)
+      .def("fgsm", &MnistEngine::fgsm, "", {torch::arg("x"), torch::arg("y"), torch::arg("eps"), torch::arg("adv_rows") = -1})
+      .def("set_adversarial", &MnistEngine::set_adversarial, "", {torch::arg("eps"), torch::arg("adv_rows") = -1})
+      .def("adversarial", &MnistEngine::adversarial)
       .def("set_keep_prob", &MnistEngine::set_keep_prob)
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -95,6 +95,13 @@ def main(argv=None):
     ap.add_argument("--elastic_alpha", type=float, default=0.0, help="augmentation: elastic distortion, displacement "
                     "scale in pixels (Simard et al.: 34 with sigma 4)")
     ap.add_argument("--elastic_sigma", type=float, default=0.0, help="--elastic_alpha: the Gaussian's sigma in pixels")
+    ap.add_argument("--adv_eps", type=float, default=0.0, help="FGSM adversarial training: every step trains on "
+                    "clip(x + eps * sign(dL/dx), 0, 1) of its rows, perturbed with the step's own parameters (GPU: a pre-pass "
+                    "at the head of every step, inside the step graph, csrc/mnist_input_grad.h; CPU: fp64 autograd); 0 = off")
+    ap.add_argument("--adv_rows", type=int, default=-1, help="--adv_eps: only the first this many rows of a batch are "
+                    "perturbed (batch_size / 2: the half-clean batch of Kurakin et al.); -1 = all")
+    ap.add_argument("--adv_eval_eps", type=float, default=0.0, help="also print the accuracy of the final evaluation's "
+                    "rows under FGSM at this eps (Adversarial Testing Accuracy); 0 = off")
     ap.add_argument("--device_eval", action="store_true", help="upload the validation split once and evaluate it on "
                     "the device: the --eval_batches x 100 rows in split order (not next_batch's shuffle: the same mean "
                     "whenever they are the whole split, as the default 50 x 100 are), one record per batch folded by the "
@@ -127,6 +134,12 @@ def main(argv=None):
     if augment_on(augment_config(*augment)) and a.host_feed and not a.cpu and torch.cuda.is_available():
         ap.error("--augment_* / --elastic_* with --host_feed: the device kernel warps rows of the device-resident "
                  "split; a host-fed GPU run has none")
+    if a.adv_eps < 0 or a.adv_eval_eps < 0 or a.adv_rows < -1 or a.adv_rows > a.batch_size:
+        ap.error("--adv_eps and --adv_eval_eps must be >= 0, --adv_rows in [0, batch_size] or -1 (all)")
+    if a.adv_eps > 0 and a.grad_accum_steps > 1:
+        ap.error("--adv_eps with --grad_accum_steps > 1: the adversarial pre-pass perturbs one batch, not K micro-batches")
+    if (a.adv_eps > 0 or a.adv_eval_eps > 0) and a.dtype == "fp32" and not a.cpu and torch.cuda.is_available():
+        ap.error("--adv_eps / --adv_eval_eps with --dtype fp32: the input-gradient kernel reads the bf16 step's operands")
     step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
@@ -163,6 +176,8 @@ def main(argv=None):
         runner.set_device_dataset(mnist.train.images, mnist.train.labels, seed=a.seed + 101)
     if augment_on(augment_config(*augment)):
         runner.set_augment(*augment)
+    if a.adv_eps > 0:
+        runner.set_adversarial(a.adv_eps, a.adv_rows)
 
     start_time = time.time()
     train_flag = a.train_flag
@@ -220,18 +235,31 @@ def main(argv=None):
     if a.ema_decay > 0:
         print("Accuracy from the %s" % ("moving averages (decay %g)" % a.ema_decay if use_ema else "variables"))
     accuracy_arr = []
+    adv_correct = adv_n = 0
+
+    def adversarial_rows(x, y):  # the same rows once more, under FGSM at --adv_eval_eps
+        _, c = runner.evaluate(runner.fgsm(x, y, a.adv_eval_eps), y, use_ema=use_ema)
+        return c, len(x)
     if a.device_eval:
         # the split uploaded once, rows in split order; one record per batch of 100 from one call
         runner.set_eval_dataset(mnist.validation.images, mnist.validation.labels)
         recs = runner.evaluate_dataset(0, min(nt * 100, mnist.validation.num_examples), 100, use_ema=use_ema)
         accuracy_arr = [r["correct"] / float(r["rows"]) for r in recs]
+        if a.adv_eval_eps > 0:
+            rows = min(nt * 100, mnist.validation.num_examples)
+            adv_correct, adv_n = adversarial_rows(mnist.validation.images[:rows], mnist.validation.labels[:rows])
     else:
         for counter in range(1, nt + 1):
             val_x, val_y = mnist.validation.next_batch(100)
             _, correct = runner.evaluate(val_x, val_y, use_ema=use_ema)
             accuracy_arr.append(correct / float(len(val_x)))
+            if a.adv_eval_eps > 0:
+                c, n = adversarial_rows(val_x, val_y)
+                adv_correct, adv_n = adv_correct + c, adv_n + n
     mean_accuracy = sum(accuracy_arr) / len(accuracy_arr)
     print("Mean Accuracy : %f" % mean_accuracy)
+    if a.adv_eval_eps > 0:
+        print("Adversarial Testing Accuracy (eps=%g) : %f" % (a.adv_eval_eps, adv_correct / float(adv_n)))
     if a.confusion_matrix:
         print(inference.format_confusion(inference.merge_records(recs)["confusion"]))
     testing_end_time = time.time()

@@ -226,6 +226,7 @@ class TorchMnistRunner(MnistRunnerBase):
         self._log_sums = []  # (loss sum, correct, rows) of the current step's micro-batches
         self._seed, self._rank = int(seed), int(rank)
         self._aug = None    # augmentation config (set_augment), None = off
+        self._adv = (0.0, -1)  # FGSM adversarial training (set_adversarial): (eps, adv_rows), eps 0 = off
 
     def params(self) -> torch.Tensor:
         return self.flat
@@ -315,6 +316,8 @@ class TorchMnistRunner(MnistRunnerBase):
         self._log_sums = []
         if self._aug is not None:
             x = self._augmented(x)
+        if self._adv[0] > 0:
+            x = self.fgsm(x, y, *self._adv)
         if K == 1:
             g, _ = self.compute_grads(x, y)
             if self.comm is not None:
@@ -349,6 +352,26 @@ class TorchMnistRunner(MnistRunnerBase):
         x = _as_f32(x)
         draws = native_augment_draws(x.shape[0], self._step, self._rank, self._seed)
         return torch.from_numpy(warp_rows_ref(x.cpu().numpy(), self._aug, draws)).float()
+
+    # ---- input gradient and FGSM: training/adversarial.py's fp64 definitions ----
+    def input_gradient(self, x, y) -> torch.Tensor:
+        """``d mean_loss / d x`` [n,784] fp32 at ``keep_prob = 1``; the mean is over the ``n`` rows given."""
+        from ..training.adversarial import input_gradient_ref
+
+        return torch.from_numpy(input_gradient_ref(self.flat, _as_f32(x).cpu().numpy(), _labels_to_ids(y).cpu().numpy())).float()
+
+    def fgsm(self, x, y, eps: float, adv_rows: int = -1) -> torch.Tensor:
+        """``clip(x + eps * sign(dL/dx), 0, 1)`` for rows ``< adv_rows`` (-1: all), the other rows copied."""
+        from ..training.adversarial import fgsm_ref
+
+        return torch.from_numpy(fgsm_ref(self.flat, _as_f32(x).cpu().numpy(), _labels_to_ids(y).cpu().numpy(), eps, adv_rows))
+
+    def set_adversarial(self, eps: float = 0.0, adv_rows: int = -1) -> None:
+        """FGSM adversarial training: every ``train_step`` trains on ``fgsm`` of its rows (augmented first).
+        ``eps = 0`` turns it off. Refuses gradient accumulation, as the device engine does."""
+        if eps > 0 and self.accum_steps > 1:
+            raise ValueError("set_adversarial with accum_steps > 1: the pre-pass perturbs one batch, not K micro-batches")
+        self._adv = (float(eps), int(adv_rows)) if eps > 0 else (0.0, -1)
 
     # ---- step log: the device runner's three methods over a plain Python ring ----
     def set_step_log(self, capacity: int = 1024) -> None:
@@ -593,6 +616,41 @@ class NativeMnistRunner(MnistRunnerBase):
 
     def augment(self) -> dict:
         return dict(zip(("shift", "rotate", "scale", "elastic_alpha", "elastic_sigma"), self.eng.augment()))
+
+    # ---- input gradient and FGSM on the device (csrc/mnist_input_grad.h) ----
+    def _rows_on_device(self, x, y):
+        return _as_f32(x).to(self.device).contiguous(), _labels_to_ids(y).to(self.device).contiguous()
+
+    def input_gradient(self, x, y) -> torch.Tensor:
+        """``d mean_loss / d x`` [n,784] fp32 at ``keep_prob = 1``, rows in chunks of the engine's batch (the
+        mean is over a chunk's rows). Training state, ``loss_rows`` and ``correct_rows`` keep their bits."""
+        x, y = self._rows_on_device(x, y)
+        with torch.cuda.stream(self.stream):
+            dx = self.eng.input_gradient(x, y)
+        self.stream.synchronize()
+        return dx
+
+    def fgsm(self, x, y, eps: float, adv_rows: int = -1) -> torch.Tensor:
+        """``clip(x + eps * sign(dL/dx), 0, 1)`` for rows ``< adv_rows`` (-1: all), the other rows copied."""
+        x, y = self._rows_on_device(x, y)
+        with torch.cuda.stream(self.stream):
+            xadv = self.eng.fgsm(x, y, float(eps), int(adv_rows))
+        self.stream.synchronize()
+        return xadv
+
+    def set_adversarial(self, eps: float = 0.0, adv_rows: int = -1) -> None:
+        """FGSM adversarial training inside the step graph: every training step body starts with a pre-pass
+        that perturbs the rows it would read (rows ``< adv_rows``; -1: all) with the step's own parameters.
+        ``eps = 0`` turns it off. bf16 engine, no gradient accumulation, one GPU or all-reduce DP; the captured
+        graphs are dropped."""
+        self.stream.synchronize()  # the engine drops its graphs: none may still be running
+        with torch.cuda.stream(self.stream):
+            self.eng.set_adversarial(float(eps), int(adv_rows))
+        self._stale_graphs()
+        self._grads_graph = False
+
+    def adversarial(self) -> dict:
+        return dict(zip(("eps", "adv_rows"), self.eng.adversarial()))
 
     def read_step_log(self, first_t: int, last_t: int) -> list:
         """The records of optimizer steps ``first_t..last_t`` (``t`` = global_step after the step) as dicts

@@ -209,6 +209,14 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("augment_scale", 0.0, "Augmentation: random scale in [1 - s, 1 + s], s < 1")
     f.DEFINE_float("elastic_alpha", 0.0, "Augmentation: elastic distortion (Simard et al.), displacement scale in pixels")
     f.DEFINE_float("elastic_sigma", 0.0, "--elastic_alpha: sigma of the Gaussian that smooths the displacement field, pixels")
+    f.DEFINE_float("adv_eps", 0.0, "FGSM adversarial training (--model mnist_cnn, one worker or synchronous all-reduce DP, "
+                   "bf16): every step trains on clip(x + eps * sign(dL/dx), 0, 1) of its rows, perturbed with the step's own "
+                   "parameters. GPU: a pre-pass at the head of every step body, inside the step graph "
+                   "(csrc/mnist_input_grad.h); CPU: fp64 autograd (training/adversarial.py). 0 = off")
+    f.DEFINE_integer("adv_rows", -1, "--adv_eps: only the first this many rows of a worker's batch are perturbed "
+                     "(batch_size / 2: the half-clean batch of Kurakin et al.); -1 = all")
+    f.DEFINE_float("adv_eval_eps", 0.0, "Also print, after the final evaluation, the accuracy of the same rows under FGSM "
+                   "at this eps (Adversarial Testing Accuracy); 0 = off")
 
 
 def _make_learning_rate():
@@ -399,6 +407,32 @@ def check_augment_flags(num_workers: int) -> bool:
         raise ValueError("%s with --device_input=False: the device kernel warps rows of the device-resident split; a "
                          "host-fed GPU run has none" % which)
     return True
+
+
+def check_adversarial_flags(num_workers: int) -> bool:
+    """Whether --adv_eps turns adversarial training on. What --adv_eps / --adv_eval_eps do not cover is a flag error,
+    raised before any process group is built (every rank sees the same flags)."""
+    if FLAGS.adv_eps < 0 or FLAGS.adv_eval_eps < 0 or FLAGS.adv_rows < -1 or FLAGS.adv_rows > FLAGS.batch_size:
+        raise ValueError("--adv_eps and --adv_eval_eps must be >= 0, --adv_rows in [0, batch_size] or -1 (all)")
+    if not (FLAGS.adv_eps > 0 or FLAGS.adv_eval_eps > 0):
+        return False
+    which = "--adv_eps / --adv_eval_eps"
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts)):
+        raise ValueError("%s with a parameter-server mode (%s): the worker's step there is a bare forward and backward on "
+                         "fed rows; the adversarial pre-pass belongs to the engine's training step"
+                         % (which, "--sync_replicas=False" if not FLAGS.sync_replicas else "backup workers"))
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the input-gradient kernel is the MNIST CNN's" % (which, FLAGS.model))
+    if FLAGS.num_gpus > 0 and FLAGS.dtype == "fp32":
+        raise ValueError("%s with --dtype fp32: the input-gradient kernel reads the bf16 step's operands" % which)
+    if FLAGS.adv_eps > 0:
+        if FLAGS.grad_accum_steps > 1:
+            raise ValueError("--adv_eps with --grad_accum_steps > 1: the pre-pass perturbs one batch, not K micro-batches")
+        if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
+            raise ValueError("--adv_eps with --dp_schedule %s: the pre-pass needs whole parameters and buffers of its own on "
+                             "every rank; use --dp_schedule allreduce" % FLAGS.dp_schedule)
+    return FLAGS.adv_eps > 0
 
 
 def check_steps_per_call_flags(num_workers: int) -> None:
@@ -693,8 +727,9 @@ def dp_candidates(device_type: str, dtype: str):
         # --grad_accum_steps: the micro-batch gradients are summed whole before the one collective
         # (MnistEngine.set_grad_accum)
         # --skip_nonfinite: the guard reads the whole aggregated gradient (MnistEngine.set_skip_nonfinite)
+        # --adv_eps: the adversarial pre-pass needs whole parameters and buffers of its own (MnistEngine.set_adversarial)
         if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS or \
-                FLAGS.grad_accum_steps > 1 or FLAGS.skip_nonfinite:
+                FLAGS.grad_accum_steps > 1 or FLAGS.skip_nonfinite or FLAGS.adv_eps > 0:
             return ["allreduce"]
         # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
         return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
@@ -889,6 +924,7 @@ def main(argv=None) -> int:
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
     check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))
     check_augment_flags(len(FLAGS.worker_hosts.split(",")))
+    check_adversarial_flags(len(FLAGS.worker_hosts.split(",")))
     check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
@@ -983,6 +1019,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
             raise ValueError("--augment_* / --elastic_*: %s feeds the GPU engine from the host; the device kernel "
                              "warps rows of the device-resident split" % gsync.describe())
         runner.set_augment(*augment_flags())
+    if check_adversarial_flags(num_workers):
+        runner.set_adversarial(FLAGS.adv_eps, FLAGS.adv_rows)
 
     sv = _prepare_session(cluster, is_chief, runner,
                           lambda: runner.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0), gsync.broadcast)
@@ -1017,8 +1055,16 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
               "%d worker(s); steps are optimizer steps" % (FLAGS.task_index, accum, FLAGS.batch_size,
                                                           step_rows * (num_workers if sync else 1), num_workers))
 
+    adv_eval = {"on": False, "rows": 0, "correct": 0}  # --adv_eval_eps: the final evaluation's rows under FGSM
+
+    def adversarial_rows(x, y):
+        adv_eval["rows"] += len(x)
+        adv_eval["correct"] += runner.evaluate(runner.fgsm(x, y, FLAGS.adv_eval_eps), y, use_ema=ema_eval)[1]
+
     def eval_batch():
         val_x, val_y = mnist.validation.next_batch(FLAGS.eval_batch_size)
+        if adv_eval["on"]:
+            adversarial_rows(val_x, val_y)
         return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
 
     eval_rows = min(FLAGS.eval_batches * FLAGS.eval_batch_size, mnist.validation.num_examples)
@@ -1175,12 +1221,16 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     print("Worker %d: %.1f images/sec (%d optimizer steps of %d images)" % (
         FLAGS.task_index, step_rows * (num_workers if sync else 1) * local_step / max(training_time, 1e-9), local_step,
         step_rows * (num_workers if sync else 1)))
+    adv_eval["on"] = FLAGS.adv_eval_eps > 0
     if FLAGS.device_eval:
         batches, recs = eval_pass()
         mean_accuracy = _validate(iter(batches).__next__, len(batches))
         whole = inference.merge_records(recs)
         evaluation = dict(event="evaluation", global_step=step, rows=whole["rows"], correct=whole["correct"],
                           loss=whole["loss_sum"] / max(whole["rows"], 1), mean_accuracy=mean_accuracy)
+        if adv_eval["on"]:
+            adversarial_rows(mnist.validation.images[:eval_rows], mnist.validation.labels[:eval_rows])
+            evaluation.update(adv_accuracy=adv_eval["correct"] / float(max(adv_eval["rows"], 1)), adv_eps=FLAGS.adv_eval_eps)
         if FLAGS.confusion_matrix:
             print(inference.format_confusion(whole["confusion"]))
             evaluation.update(confusion=whole["confusion"].tolist(),
@@ -1189,6 +1239,11 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         metrics.log(**evaluation)
     else:
         mean_accuracy = _validate(eval_batch)
+        if adv_eval["on"]:
+            metrics.log(event="evaluation", global_step=step, rows=adv_eval["rows"], mean_accuracy=mean_accuracy,
+                        adv_accuracy=adv_eval["correct"] / float(max(adv_eval["rows"], 1)), adv_eps=FLAGS.adv_eval_eps)
+    if adv_eval["on"]:
+        print("Adversarial Testing Accuracy (eps=%g) : %f" % (FLAGS.adv_eval_eps, adv_eval["correct"] / float(max(adv_eval["rows"], 1))))
     skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
     if skipped > 0:
         print("Worker %d: --skip_nonfinite skipped %d of %d optimizer steps (aggregated gradient not finite)"
