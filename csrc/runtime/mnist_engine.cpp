@@ -29,6 +29,7 @@
 #include "../mnist_infer.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
+#include "../optim_q8.h"
 #include "../optim_rules.h"
 #include "../step_log.h"
 #include "../tfd_kernels.h"
@@ -41,7 +42,7 @@ using namespace mnist;
 
 class MnistEngine : public torch::CustomClassHolder {
   // the update rule (not part of the torch class); LAMB runs on Adam's settings and slots, LARS on Momentum's
-  enum class OptKind { Adam, Sgd, Momentum, RmsProp, Adagrad };
+  enum class OptKind { Adam, Sgd, Momentum, RmsProp, Adagrad, Adam8 };
   enum class LwKind { None, Lamb, Lars };
  public:
   MnistEngine(int64_t batch, int64_t device, double keep_prob, int64_t seed, int64_t rank)
@@ -111,8 +112,10 @@ class MnistEngine : public torch::CustomClassHolder {
   at::Tensor grads() { return grad_; }
   // bf16 gradient buffer: the DP wire format (reduced in place by the bucket all-reduces)
   at::Tensor grads_bf16() { return gbf_; }
-  at::Tensor adam_m() { return m_; }
-  at::Tensor adam_v() { return v_; }
+  // the fp32 slots; with 8-bit Adam on (set_adam8) decoded fp32 COPIES of its state: a write into one is lost.
+  // Whoever overwrites the 8-bit state writes adam8_state()'s tensors or calls load_adam8
+  at::Tensor adam_m() { return opt_ == OptKind::Adam8 ? q8_decoded(m8_, am_, Q8_M) : m_; }
+  at::Tensor adam_v() { return opt_ == OptKind::Adam8 ? q8_decoded(v8_, av_, Q8_V) : v_; }
   // the third slot (centered RMSProp's mg): allocated at the first set_rmsprop(centered = true)
   at::Tensor slot3() {
     TORCH_CHECK(s3_.defined(), "slot3: set_rmsprop(centered = true) first");
@@ -394,6 +397,41 @@ class MnistEngine : public torch::CustomClassHolder {
       if (!s3_.defined()) s3_ = at::zeros_like(m_);
       else s3_.zero_();
     }
+  }
+  // 8-bit Adam (csrc/optim_q8.h, kernels/optim_q8.hip): both moments as fp8 codes with one fp32 scale per 256
+  // flat elements, updated by ONE launch over [0, TOTAL) on the unfused step -- the path Momentum and the rules
+  // take; in DP on the whole-gradient schedule of the clip step, since a block may straddle the two buckets. The
+  // state starts as m = v = 0 (codes 0, scales 0) and is allocated at the first call; adam_m() / adam_v() keep
+  // their fp32 buffers for the other optimizers. Composes with set_lr_schedule, set_clip_norm, set_ema,
+  // set_skip_nonfinite, set_grad_accum, both dtypes and the all-reduce DP schedule; the step refuses ZeRO-1 and
+  // SFB. Baked into graphs captured before the call.
+  void set_adam8(double lr, double b1, double b2, double eps) {
+    b1_ = b1; b2_ = b2; eps_ = eps;
+    if (!m8_.defined()) {
+      auto u8 = at::TensorOptions().dtype(at::kByte).device(params_.device());
+      m8_ = at::zeros({TOTAL}, u8);
+      v8_ = at::zeros({TOTAL}, u8);
+      am_ = at::zeros({q8_blocks(TOTAL)}, params_.options());
+      av_ = at::zeros({q8_blocks(TOTAL)}, params_.options());
+    } else {
+      for (at::Tensor* t : {&m8_, &v8_, &am_, &av_}) t->zero_();
+    }
+    set_optimizer(OptKind::Adam8, lr);
+  }
+  // {m8, v8, am, av}: the state itself (views share storage with the engine)
+  std::vector<at::Tensor> adam8_state() {
+    TORCH_CHECK(m8_.defined(), "adam8_state: set_adam8 first");
+    return {m8_, v8_, am_, av_};
+  }
+  // fp32 slots -> the state, by the kernels' own encode; decode followed by this reproduces codes and scales
+  void load_adam8(at::Tensor m, at::Tensor v) {
+    TORCH_CHECK(m8_.defined(), "load_adam8: set_adam8 first");
+    TORCH_CHECK(m.numel() == TOTAL && v.numel() == TOTAL, "load_adam8: ", TOTAL, " elements each");
+    at::Tensor src[2] = {m.reshape({TOTAL}).to(params_.options()).contiguous(), v.reshape({TOTAL}).to(params_.options()).contiguous()};
+    q8_encode_launch(Q8CodecArgs{(float*)src[0].data_ptr(), (uint8_t*)m8_.data_ptr(), (float*)am_.data_ptr(), TOTAL, Q8_M}, stream());
+    q8_encode_launch(Q8CodecArgs{(float*)src[1].data_ptr(), (uint8_t*)v8_.data_ptr(), (float*)av_.data_ptr(), TOTAL, Q8_V}, stream());
+    // the sources may be temporaries: they must outlive the launches that read them
+    HIP_OK(hipStreamSynchronize(stream()));
   }
   void set_adagrad(double lr, double initial_accumulator_value) {
     TORCH_CHECK(initial_accumulator_value > 0, "set_adagrad: initial_accumulator_value > 0");
@@ -753,6 +791,10 @@ class MnistEngine : public torch::CustomClassHolder {
       apply_layerwise(bf_grads, grad_scale, t_offset, tsrc, m, s);
     } else if (is_rule()) {
       apply_rule(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc, m, s);
+    } else if (opt_ == OptKind::Adam8) {
+      TORCH_CHECK(beg == 0 && end == TOTAL, "8-bit Adam updates the whole flat buffer: its 256-element blocks follow the "
+                  "flat index and a range may cut one");
+      apply_adam8(bf_grads, grad_scale, t_offset, tsrc, m, s);
     } else if (opt_ == OptKind::Adam) {
       adam_launch(adam_args(beg, end - beg, bf_grads, grad_scale, t_offset, tsrc), m, s);
     } else {
@@ -797,6 +839,11 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(adv_on_ && (zero_ || sfb_active())), "set_adversarial conflicts with ", zero_ ? "ZeRO-1 (set_zero)" :
                 "sufficient-factor fc gradients (set_fc_sfb)", ": the pre-pass needs whole parameters and buffers of its "
                 "own on every rank; use the all-reduce schedule");
+    // one launch over the whole buffer: a shard or a bucket may cut a 256-element block
+    TORCH_CHECK(!(opt_ == OptKind::Adam8 && (zero_ || sfb_active())), "set_adam8 conflicts with ",
+                zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
+                ": the 8-bit state's blocks follow the flat index and are updated in one launch over the whole "
+                "aggregated gradient; use the all-reduce schedule");
     if (zero_ && !sfb_active()) {
       train_step_zero();
       return;
@@ -809,7 +856,7 @@ class MnistEngine : public torch::CustomClassHolder {
       train_step_accum(dp);
       return;
     }
-    if (clip_norm_ > 0 || layerwise() || guard_) {
+    if (clip_norm_ > 0 || layerwise() || guard_ || (dp && opt_ == OptKind::Adam8)) {
       train_step_clip(dp);
       return;
     }
@@ -1843,6 +1890,33 @@ class MnistEngine : public torch::CustomClassHolder {
     if (rms) rmsprop_apply(a, centered_, s);
     else adagrad_apply(a, s);
   }
+  // 8-bit Adam over [0, TOTAL); m: the step's modifiers (mods(0, ...))
+  void apply_adam8(bool bf_grads, double grad_scale, int t_offset, const int64_t* t, const OptMods& m, hipStream_t s) {
+    Adam8Args a{};
+    a.p = (float*)params_.data_ptr();
+    a.m8 = (uint8_t*)m8_.data_ptr();
+    a.v8 = (uint8_t*)v8_.data_ptr();
+    a.am = (float*)am_.data_ptr();
+    a.av = (float*)av_.data_ptr();
+    a.g = bf_grads ? nullptr : (const float*)grad_.data_ptr();
+    a.gbf = bf_grads ? (const uint16_t*)gbf_.data_ptr() : nullptr;
+    a.pbf = (uint16_t*)pbf_.data_ptr();
+    a.n = TOTAL;
+    a.sched = sched_;
+    a.beta1 = (float)b1_;
+    a.beta2 = (float)b2_;
+    a.eps = (float)eps_;
+    a.step = t;
+    a.t_offset = t_offset;
+    a.grad_scale = (float)grad_scale;
+    apply_mods(a, m);
+    adam8_apply(a, s);
+  }
+  at::Tensor q8_decoded(const at::Tensor& codes, const at::Tensor& absmax, int kind) {
+    at::Tensor x = at::empty({TOTAL}, params_.options());
+    q8_decode_launch(Q8CodecArgs{(float*)x.data_ptr(), (uint8_t*)codes.data_ptr(), (float*)absmax.data_ptr(), TOTAL, kind}, stream());
+    return x;
+  }
   // What a step adds to the bare update over a range that starts at beg (optim_launch.h). The only reader of
   // the EMA settings and one_ for a flat launch; with the shadow it marks the shadow's bf16 image stale: an
   // EMA launch is about to move the shadow.
@@ -2168,6 +2242,7 @@ class MnistEngine : public torch::CustomClassHolder {
   double rule_decay_ = 0.9, rule_eps_ = 1e-10;
   bool centered_ = false;
   at::Tensor s3_;
+  at::Tensor m8_, v8_, am_, av_;  // 8-bit Adam's state (set_adam8)
   LwKind lw_ = LwKind::None;  // layer-wise optimizer (set_lamb / set_lars); its tables and outputs
   int lw_nblocks_ = 0;
   double lw_wd_ = 0.0, lw_eeta_ = 0.0, lw_eps_ = 0.0;
@@ -2317,6 +2392,9 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("set_momentum", &MnistEngine::set_momentum)
       .def("set_rmsprop", &MnistEngine::set_rmsprop)
       .def("set_adagrad", &MnistEngine::set_adagrad)
+      .def("set_adam8", &MnistEngine::set_adam8)
+      .def("adam8_state", &MnistEngine::adam8_state)
+      .def("load_adam8", &MnistEngine::load_adam8)
       .def("set_lamb", &MnistEngine::set_lamb)
       .def("set_lars", &MnistEngine::set_lars)
       .def("layer_norms", &MnistEngine::layer_norms)

@@ -23,8 +23,8 @@ from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: 
 from tensorflow_distributed_amd.training import checkpoint, inference  # noqa: E402
 from tensorflow_distributed_amd.training.augment import augment_config, augment_on  # noqa: E402
 from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
-from tensorflow_distributed_amd.training.optimizers import (AdagradOptimizer, AdamOptimizer, LAMBOptimizer,  # noqa: E402
-                                                            LARSOptimizer, RMSPropOptimizer)
+from tensorflow_distributed_amd.training.optimizers import (Adam8bitOptimizer, AdagradOptimizer, AdamOptimizer,  # noqa: E402
+                                                            LAMBOptimizer, LARSOptimizer, RMSPropOptimizer)
 from tensorflow_distributed_amd.utils import input_data  # noqa: E402
 
 # Parameters (mnist_single.py:17-21)
@@ -60,8 +60,8 @@ def main(argv=None):
     ap.add_argument("--skip_nonfinite", action="store_true", help="non-finite guard: a step whose gradient is not "
                     "finite (an inf / NaN element, or a norm beyond fp32) is skipped -- parameters, optimizer slots and "
                     "moving averages keep their bits (GPU: decided on the device inside the step graph)")
-    ap.add_argument("--optimizer", default="adam", choices=["adam", "lamb", "lars", "rmsprop", "adagrad"],
-                    help="adam (the reference); lamb / lars, layer-wise optimizers: every variable's update scaled by a "
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "adam8", "lamb", "lars", "rmsprop", "adagrad"],
+                    help="adam (the reference); adam8: Adam with both moments as block-scaled fp8 codes; lamb / lars, layer-wise optimizers: every variable's update scaled by a "
                     "trust ratio of two per-variable norms; rmsprop / adagrad (tf.train.RMSPropOptimizer / "
                     "AdagradOptimizer)")
     ap.add_argument("--rmsprop_decay", type=float, default=0.9, help="--optimizer rmsprop: decay of the averages")
@@ -161,6 +161,8 @@ def main(argv=None):
                                bool(a.rmsprop_centered), **common)
     elif a.optimizer == "adagrad":
         opt = AdagradOptimizer(a.learning_rate, a.adagrad_init_accum, **common)
+    elif a.optimizer == "adam8":
+        opt = Adam8bitOptimizer(a.learning_rate, **common)
     else:
         opt = AdamOptimizer(a.learning_rate, **common)
     runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,

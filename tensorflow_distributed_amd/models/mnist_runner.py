@@ -522,6 +522,10 @@ class NativeMnistRunner(MnistRunnerBase):
         elif o.kind == "adagrad":
             self.eng.set_adagrad(lr0, o.initial_accumulator_value)
             torch.cuda.current_stream(self.device).synchronize()
+        elif o.kind == "adam8":
+            # both moments as fp8 codes with one scale per 256 elements, one fused kernel (csrc/kernels/optim_q8.hip)
+            self.eng.set_adam8(lr0, o.beta1, o.beta2, o.epsilon)
+            torch.cuda.current_stream(self.device).synchronize()
         elif o.kind != "sgd":
             raise ValueError(f"NativeMnistRunner: no native rule for optimizer kind {o.kind!r}")
         else:
@@ -781,9 +785,14 @@ class NativeMnistRunner(MnistRunnerBase):
         with torch.cuda.stream(self.stream):
             self.eng.params().copy_(flat.to(self.device))
             self.eng.sync_shadow()
-            if "m" in slots or "accum" in slots:
+            if self.opt.kind == "adam8":
+                # a checkpoint carries the decoded fp32 slots; the engine re-encodes them, which reproduces the
+                # codes and scales they were decoded from
+                if "m" in slots and "v" in slots:
+                    self.eng.load_adam8(slots["m"].to(self.device), slots["v"].to(self.device))
+            elif "m" in slots or "accum" in slots:
                 self.eng.adam_m().copy_(slots.get("m", slots.get("accum")).to(self.device))
-            if "v" in slots:
+            if "v" in slots and self.opt.kind != "adam8":
                 self.eng.adam_v().copy_(slots["v"].to(self.device))
             for name, dst in self._rule_slots().items():  # RMSProp / Adagrad
                 if name in slots:
@@ -829,15 +838,22 @@ class NativeMnistRunner(MnistRunnerBase):
         self.stream.synchronize()
         if self.opt.kind in ("rmsprop", "adagrad"):
             return self._rule_slots()
-        if self.opt.kind in ("adam", "lamb"):
+        if self.opt.kind in ("adam", "lamb", "adam8"):  # adam8: decoded fp32 copies of the 8-bit state
             return {"m": self.eng.adam_m(), "v": self.eng.adam_v()}
         if self.opt.kind in ("momentum", "lars"):
             return {"accum": self.eng.adam_m()}
         return {}
 
+    def state_tensors(self) -> list:
+        """The optimizer state in place, for whoever overwrites it (a broadcast). adam8: the codes and scales --
+        slot_tensors() holds decoded copies there, and a write into a copy is lost."""
+        if self.opt.kind == "adam8":
+            return list(self.eng.adam8_state())
+        return list(self.slot_tensors().values())
+
     def powers(self):
         o = self.opt
-        if o.kind != "adam":
+        if o.kind not in ("adam", "adam8"):
             return {}
         t = self.global_step()
         return {"beta1_power": o.beta1 ** t, "beta2_power": o.beta2 ** t}
@@ -855,8 +871,9 @@ class NativeMnistRunner(MnistRunnerBase):
             return
         with torch.cuda.stream(self.stream):
             self.comm.broadcast(self.eng.params(), root)
-            self.comm.broadcast(self.eng.adam_m(), root)
-            self.comm.broadcast(self.eng.adam_v(), root)
+            # adam8: the codes and scales themselves; adam_m() / adam_v() are decoded copies there
+            for t in self.eng.adam8_state() if self.opt.kind == "adam8" else (self.eng.adam_m(), self.eng.adam_v()):
+                self.comm.broadcast(t, root)
             if self.opt.kind == "rmsprop" and self.opt.centered:
                 self.comm.broadcast(self.eng.slot3(), root)
             self.comm.broadcast(self.eng.step_tensor(), root)

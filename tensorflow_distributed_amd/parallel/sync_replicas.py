@@ -99,7 +99,9 @@ def broadcast_state(runner, src_worker: int = 0, group=None, group_src_rank: Opt
         runner.broadcast_from(src_worker)
         return
     src = group_src_rank if group_src_rank is not None else src_worker
-    tensors = [runner.params()] + list(runner.slot_tensors().values())
+    # the state in place: a native adam8 runner's slot_tensors() are decoded copies, whose overwriting is lost
+    state = runner.state_tensors() if hasattr(runner, "state_tensors") else list(runner.slot_tensors().values())
+    tensors = [runner.params()] + state
     ema = runner.ema_params() if getattr(runner, "ema_on", False) else None  # read before params() is overwritten
     for t in tensors:
         buf = t.detach().cpu().contiguous()

@@ -117,8 +117,9 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
     f.DEFINE_float("save_summaries_secs", 120.0, "Summary (global_step/sec) period (chief)")
     f.DEFINE_integer("seed", 0, "Init seed (normal(0,1) params, chief)")
     f.DEFINE_float("keep_prob", 0.75, "Dropout keep probability during training")
-    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum", "lamb", "lars", "rmsprop", "adagrad"],
-                  "Optimizer (reference: adam). lamb "
+    f.DEFINE_enum("optimizer", "adam", ["adam", "sgd", "momentum", "lamb", "lars", "rmsprop", "adagrad", "adam8"],
+                  "Optimizer (reference: adam). adam8: Adam with both moments as block-scaled fp8 codes (one fused "
+                  "kernel; --model mnist_cnn, synchronous all-reduce training). lamb "
                   "and lars scale every variable's update by a trust ratio formed from two per-variable L2 norms "
                   "(on GPUs on the device, inside the step graph); synchronous all-reduce training of --model "
                   "mnist_cnn only. rmsprop and adagrad (tf.train.RMSPropOptimizer / AdagradOptimizer): --model "
@@ -238,8 +239,8 @@ def _make_learning_rate():
 
 
 def _make_optimizer():
-    from .optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer,
-                             MomentumOptimizer, RMSPropOptimizer)
+    from .optimizers import (Adam8bitOptimizer, AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer, LAMBOptimizer,
+                             LARSOptimizer, MomentumOptimizer, RMSPropOptimizer)
 
     lr = _make_learning_rate()
     clip = FLAGS.clip_norm if FLAGS.clip_norm > 0 else None
@@ -262,6 +263,8 @@ def _make_optimizer():
                                 bool(FLAGS.rmsprop_centered), clip_norm=clip, accum_steps=acc, **ema)
     if FLAGS.optimizer == "adagrad":
         return AdagradOptimizer(lr, FLAGS.adagrad_init_accum, clip_norm=clip, accum_steps=acc, **ema)
+    if FLAGS.optimizer == "adam8":
+        return Adam8bitOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
     return AdamOptimizer(lr, clip_norm=clip, accum_steps=acc, **ema)
 
 
@@ -313,6 +316,23 @@ def check_rules_flags(num_workers: int) -> None:
         raise ValueError("%s with the GPU-resident parameter server: its shards know Adam, GradientDescent and "
                          "Momentum only (follow-up); pass --ps_on_gpu=False for the host parameter server, which "
                          "applies every rule" % which)
+
+
+def check_adam8_flags(num_workers: int) -> None:
+    """--optimizer=adam8 keeps one scale per 256 flat elements and updates the whole aggregated gradient in one
+    launch. The combinations it does not cover are flag errors, raised before any process group is built."""
+    if FLAGS.optimizer != "adam8":
+        return
+    which = "--optimizer=adam8"
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the ResNet runner's bucketed optimizer has no 8-bit state" % (which, FLAGS.model))
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers):
+        raise ValueError("%s with a parameter server (--sync_replicas=False or backup workers): its shards cut the "
+                         "256-element blocks of the 8-bit state; use synchronous all-reduce training" % which)
+    if FLAGS.dp_schedule not in ("fixed", "auto", "allreduce", "flat", "buckets"):
+        raise ValueError("%s with --dp_schedule=%s: the SFB / ZeRO schedules update shards and buckets, which cut the "
+                         "256-element blocks of the 8-bit state; use the all-reduce schedule" % (which, FLAGS.dp_schedule))
 
 
 def check_grad_accum_flags(num_workers: int) -> None:
@@ -728,8 +748,9 @@ def dp_candidates(device_type: str, dtype: str):
         # (MnistEngine.set_grad_accum)
         # --skip_nonfinite: the guard reads the whole aggregated gradient (MnistEngine.set_skip_nonfinite)
         # --adv_eps: the adversarial pre-pass needs whole parameters and buffers of its own (MnistEngine.set_adversarial)
+        # --optimizer=adam8: one launch over the whole flat buffer, whose 256-element blocks a shard or bucket cuts
         if dtype != "bf16" or FLAGS.clip_norm > 0 or FLAGS.optimizer in LAYERWISE_OPTIMIZERS or \
-                FLAGS.grad_accum_steps > 1 or FLAGS.skip_nonfinite or FLAGS.adv_eps > 0:
+                FLAGS.grad_accum_steps > 1 or FLAGS.skip_nonfinite or FLAGS.adv_eps > 0 or FLAGS.optimizer == "adam8":
             return ["allreduce"]
         # --ema_decay: under ZeRO-1 a rank would hold only its fc1 shard of the averages (MnistEngine.set_ema)
         return [k for k, v in SCH.MNIST_SCHEDULES.items() if not (FLAGS.ema_decay > 0 and v["zero"])]
@@ -920,6 +941,7 @@ def main(argv=None) -> int:
     check_grad_accum_flags(len(FLAGS.worker_hosts.split(",")))
     check_layerwise_flags(len(FLAGS.worker_hosts.split(",")))
     check_rules_flags(len(FLAGS.worker_hosts.split(",")))
+    check_adam8_flags(len(FLAGS.worker_hosts.split(",")))
     check_ema_flags(len(FLAGS.worker_hosts.split(",")))
     check_skip_nonfinite_flags(len(FLAGS.worker_hosts.split(",")))
     check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))

@@ -69,6 +69,7 @@ from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 MAX_BOUNDARIES = 4  # csrc/lr_schedule.h: kLrMaxBoundaries
@@ -385,6 +386,86 @@ def adam_update(p, m, v, g, t: int, lr: float, beta1: float, beta2: float, epsil
     return p - lr_t * m2 / (v2.sqrt() + epsilon), m2, v2
 
 
+@dataclass
+class Adam8bitOptimizer:
+    """Adam with both moments kept as 8-bit codes: ``m`` as ``float8_e4m3fn``, ``v`` as ``float8_e5m2``, each with
+    one fp32 scale (the block's maximum magnitude) per 256 flat elements (:func:`q8_encode`). Every update decodes
+    the state, applies :func:`adam_update` and encodes ``m'`` and ``v'``; ``p'`` is formed from the unquantised
+    ones (``csrc/optim_q8.h``). Checkpoints carry the decoded slots under Adam's names."""
+    learning_rate: LearningRate = 0.001
+    beta1: float = 0.9
+    beta2: float = 0.999
+    epsilon: float = 1e-8
+    name: str = "Adam"
+    kind: str = field(default="adam8", init=False)
+    clip_norm: Optional[float] = None
+    ema_decay: Optional[float] = None
+    ema_num_updates: bool = False
+    accum_steps: int = 1  # micro-batches summed per update (gradient accumulation); 1 = off
+    skip_nonfinite: bool = False  # non-finite guard: a step whose aggregated gradient is not finite is skipped
+
+    def __post_init__(self):
+        _check_ema(self.ema_decay)
+        _check_accum(self.accum_steps)
+
+
+Q8_BLOCK = 256  # csrc/optim_q8.h: kQ8Block
+# csrc/optim_q8.h: kQ8Tiny. A block whose maximum is below it is stored as the zero block: T / a is inf for a below
+# T / FLT_MAX, and 0 * inf = NaN would reach the codes of a block whose moments decay under a zero gradient
+Q8_TINY = np.float32(2.0 ** -90)
+# kind -> (code format, the normalised value of the block's maximum T, 1 / T): both T are powers of two and codes
+_Q8_KINDS = {"m": (torch.float8_e4m3fn, 256.0, 2.0 ** -8), "v": (torch.float8_e5m2, 32768.0, 2.0 ** -15)}
+
+
+def q8_blocks(n: int) -> int:
+    """Blocks of ``n`` flat elements: block ``k`` covers ``[256 k, min(256 k + 256, n))``."""
+    return -(-int(n) // Q8_BLOCK)
+
+
+def q8_encode(x, kind: str):
+    """``(codes uint8[n], absmax float32[q8_blocks(n)])`` of the values ``x``, in the fp32 arithmetic of
+    ``csrc/optim_q8.h``: per block ``a = max |x|``, taken as 0 below ``Q8_TINY`` (the zero block: scale 0, codes
+    0), ``inv = T / a`` (one fp32 division; 0 for ``a == 0``), ``code = cvt(x * inv)`` rounded to nearest even by
+    torch's float8 cast, finite for every finite block. ``kind`` ``"m"``: e4m3, T = 256; ``"v"``: e5m2,
+    T = 32768, and outside the zero block a positive value whose code would be 0 takes code 1. The element that
+    attains ``a`` gets the code of T and decodes to exactly ``a``, so :func:`q8_decode` followed by ``q8_encode``
+    over the same blocks reproduces codes and scales."""
+    dt, target, _ = _Q8_KINDS[kind]
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32)).ravel()
+    n, nb = x.size, q8_blocks(x.size)
+    blk = np.zeros(nb * Q8_BLOCK, dtype=np.float32)
+    blk[:n] = x
+    blk = blk.reshape(nb, Q8_BLOCK)
+    absmax = np.abs(blk).max(axis=1).astype(np.float32)
+    absmax = np.where(absmax >= Q8_TINY, absmax, np.float32(0.0)).astype(np.float32)  # the zero block
+    with np.errstate(divide="ignore"):
+        inv = np.where(absmax > 0, np.float32(target) / absmax, np.float32(0.0)).astype(np.float32)
+    y = (blk * inv[:, None]).astype(np.float32).ravel()[:n]
+    codes = torch.from_numpy(y.copy()).to(dt).view(torch.uint8).numpy().copy()
+    if kind == "v":
+        codes[(x > 0) & (codes == 0) & (np.repeat(absmax, Q8_BLOCK)[:n] > 0)] = 1
+    return codes, absmax
+
+
+def q8_decode(codes, absmax, kind: str):
+    """float32[n]: ``dec(code) * (absmax * 2^-8)`` (``"m"``) or ``dec(code) * (absmax * 2^-15)`` (``"v"``), one fp32
+    product each."""
+    dt, _, inv_target = _Q8_KINDS[kind]
+    codes = np.ascontiguousarray(np.asarray(codes, dtype=np.uint8)).ravel()
+    dec = torch.from_numpy(codes.copy()).view(dt).to(torch.float32).numpy()
+    scale = (np.asarray(absmax, dtype=np.float32).ravel() * np.float32(inv_target)).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (dec * np.repeat(scale, Q8_BLOCK)[:codes.size]).astype(np.float32)
+
+
+def adam8_update(p, m, v, g, t: int, lr: float, beta1: float, beta2: float, epsilon: float):
+    """One 8-bit Adam update from the DECODED state ``m``, ``v``: :func:`adam_update` in fp64, then ``m'`` and
+    ``v'`` rounded to fp32 and encoded. Returns ``(p', (m8', am'), (v8', av'))``; ``p'`` (fp64) is formed from the
+    unquantised ``m'`` and ``v'``."""
+    p2, m2, v2 = adam_update(p, m, v, g, t, lr, beta1, beta2, epsilon)
+    return p2, q8_encode(m2.to(torch.float32).cpu().numpy(), "m"), q8_encode(v2.to(torch.float32).cpu().numpy(), "v")
+
+
 def momentum_update(p, accum, g, lr: float, momentum: float, weight_decay: float = 0.0, nesterov: bool = False):
     """One Momentum update in fp64 (TF1 ApplyMomentum): ``(p', accum')`` with ``accum' = momentum accum + g`` and
     ``p' = p - lr accum'``, Nesterov ``p' = p - lr (g + momentum accum')``. ``accum=None`` is plain gradient
@@ -637,8 +718,10 @@ class FlatApplier:
         self.t = 0
         k = self.opt.kind
         z = lambda: torch.zeros(numel, dtype=torch.float32, device=device)  # noqa: E731
-        self.m = z() if k in ("adam", "momentum", "lamb", "lars") else None
-        self.v = z() if k in ("adam", "lamb") else None
+        # adam8: m and v hold the DECODED 8-bit state; every apply() encodes them first, which reproduces the codes
+        # and scales they were decoded from (q8_encode), so they are the state and a checkpoint of them loses nothing
+        self.m = z() if k in ("adam", "adam8", "momentum", "lamb", "lars") else None
+        self.v = z() if k in ("adam", "adam8", "lamb") else None
         # RMSProp: ms, mom and (centered) mg; Adagrad: accum -- at TF's initial values (reset_slots)
         self.ms = z() if k == "rmsprop" else None
         self.mom = z() if k == "rmsprop" else None
@@ -691,6 +774,11 @@ class FlatApplier:
             self.m.add_(g - self.m, alpha=1 - b1)
             self.v.add_(g * g - self.v, alpha=1 - b2)
             p.sub_(lr_t * self.m / (self.v.sqrt() + o.epsilon))
+        elif o.kind == "adam8":
+            p2, (m8, am), (v8, av) = adam8_update(p, self.m, self.v, g, self.t, lr, o.beta1, o.beta2, o.epsilon)
+            p.copy_(p2.to(torch.float32))
+            self.m.copy_(torch.from_numpy(q8_decode(m8, am, "m")))
+            self.v.copy_(torch.from_numpy(q8_decode(v8, av, "v")))
         elif o.kind in LAYERWISE_KINDS:
             self._apply_layerwise(p, g, lr)
         elif o.kind == "rmsprop":
@@ -761,8 +849,12 @@ class FlatApplier:
                 out[name] = getattr(self, name)
         return out
 
+    def q8_state(self):
+        """adam8: ``((m8, am), (v8, av))``, the codes and scales that ``m`` and ``v`` decode from."""
+        return q8_encode(self.m.cpu().numpy(), "m"), q8_encode(self.v.cpu().numpy(), "v")
+
     def powers(self):
         o = self.opt
-        if o.kind != "adam":
+        if o.kind not in ("adam", "adam8"):
             return {}
         return {"beta1_power": o.beta1 ** self.t, "beta2_power": o.beta2 ** self.t}
