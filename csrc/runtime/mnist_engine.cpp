@@ -25,6 +25,7 @@
 #include "../grad_accum.h"
 #include "../layerwise_kernels.h"
 #include "../mnist_augment.h"
+#include "../mnist_dp.h"
 #include "../mnist_input_grad.h"
 #include "../mnist_infer.h"
 #include "../mnist_layout.h"
@@ -172,6 +173,8 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(K >= 1 && K <= 4096, "set_grad_accum: 1 <= K <= 4096, got ", K);
     TORCH_CHECK(K == 1 || !adv_on_, "set_grad_accum(", K, ") with set_adversarial on: the adversarial pre-pass perturbs one "
                 "batch with one set of parameters, not K micro-batches; set_adversarial(0, -1) first");
+    TORCH_CHECK(K == 1 || !dp_on_, "set_grad_accum(", K, ") with set_dp_sgd on: the noise is added once per update and the "
+                "clip factors are per micro-batch row; set_dp_sgd(0, 0) first");
     if (K != accum_) {
       for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
       graphs_.clear();
@@ -351,6 +354,8 @@ class MnistEngine : public torch::CustomClassHolder {
                   "gathered slots the pre-pass would overwrite; use the all-reduce schedule");
       TORCH_CHECK(!zero_, "set_adversarial: under ZeRO-1 (set_zero) the bf16 fc1 weights are whole only after the step's "
                   "all-gather, behind the head of the body; use the all-reduce schedule");
+      TORCH_CHECK(!dp_on_, "set_adversarial: set_dp_sgd is on: the privacy analysis covers the gradient of each example's "
+                  "own loss on its own row, not a row perturbed with the batch's parameters; set_dp_sgd(0, 0) first");
     }
     const std::vector<double> user = {on ? eps : 0.0, (double)(on ? (adv_rows < 0 ? B_ : adv_rows) : -1)};
     if (user == adv_user_) return;
@@ -367,6 +372,95 @@ class MnistEngine : public torch::CustomClassHolder {
   }
   // {eps, adv_rows} in use ({0, -1}: off)
   std::vector<double> adversarial() const { return adv_user_; }
+  // ---- DP-SGD (csrc/mnist_dp.h): per-example clipping to the L2 bound C and N(0, sigma^2 C^2) noise ----
+  // While l2_norm_clip > 0 the step body is that of train_step_clip with the fc backward split around one launch:
+  //   forward, head -> mnist_backward_a part 2 (dz2) -> dp_norm_kernel (sq, norm, c; rows of dlogits, dh and dz2
+  //   scaled by c_i in place) -> mnist_backward_a part 1 -> conv backward -> conv-slab reduce (step bump)
+  //   -> dp_noise_kernel (sigma > 0) -> norm / guard, the flat optimizer, EMA, the step log, as today.
+  // The update's gradient is (sum_i c_i g_i + sigma C z) / B. It leaves the fused one-GPU tail, as set_clip_norm
+  // does: the tail forms the conv gradients inside the optimizer kernel, where no noise pass can reach them.
+  // One GPU only: with several ranks the noise has to be added once, behind the all-reduce. l2_norm_clip = 0
+  // (the default) is off: the step is launch for launch what it was. Baked into graphs: a change drops them.
+  void set_dp_sgd(double l2_norm_clip, double noise_multiplier) {
+    TORCH_CHECK(std::isfinite(l2_norm_clip) && l2_norm_clip >= 0, "set_dp_sgd: l2_norm_clip >= 0, got ", l2_norm_clip);
+    TORCH_CHECK(std::isfinite(noise_multiplier) && noise_multiplier >= 0, "set_dp_sgd: noise_multiplier >= 0, got ", noise_multiplier);
+    const bool on = l2_norm_clip > 0;
+    TORCH_CHECK(on || noise_multiplier == 0, "set_dp_sgd: noise without a clip bound has no scale; l2_norm_clip > 0");
+    if (on) {
+      TORCH_CHECK(!fp32_, "set_dp_sgd: not built for the fp32 engine (the per-example norm kernel reads the bf16 step's "
+                  "factors); set_dtype('bf16')");
+      TORCH_CHECK(accum_ == 1, "set_dp_sgd: gradient accumulation is on (grad_accum() = ", accum_, "): the noise is added "
+                  "once per update and the clip factors are per micro-batch row; set_grad_accum(1) first");
+      TORCH_CHECK(!sfb_active(), "set_dp_sgd: the sufficient-factor schedule (set_fc_sfb) gathers the fc factors before "
+                  "they could be scaled; use one GPU");
+      TORCH_CHECK(!zero_, "set_dp_sgd: under ZeRO-1 (set_zero) no rank holds the whole gradient the noise is added to; "
+                  "use one GPU");
+      TORCH_CHECK(!adv_on_, "set_dp_sgd: set_adversarial is on: the privacy analysis covers the gradient of each example's "
+                  "own loss on its own row; set_adversarial(0, -1) first");
+      TORCH_CHECK(!dp(), "set_dp_sgd: one worker only: with several ranks the noise must be added once, behind the "
+                  "all-reduce, which this schedule does not do");
+    }
+    if (on == dp_on_ && l2_norm_clip == dp_clip_ && noise_multiplier == dp_sigma_) return;
+    for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
+    graphs_.clear();
+    dp_on_ = on;
+    dp_clip_ = l2_norm_clip;
+    dp_sigma_ = noise_multiplier;
+    if (!on) return;
+    if (!dp_sq_.defined()) {
+      dp_sq_ = at::zeros({B_, 8}, loss_row_.options());
+      dp_norm_ = at::zeros({B_}, loss_row_.options());
+      dp_c_ = at::ones({B_}, loss_row_.options());
+    }
+    dp_norm_prepare();  // the dynamic-LDS limit, outside any capture
+  }
+  // {l2_norm_clip, noise_multiplier} in use ({0, 0}: off)
+  std::vector<double> dp_sgd() const { return {dp_clip_, dp_sigma_}; }
+  // the last step's per-example gradient norms [B], clip factors [B] and squared norms per variable [B][8]
+  at::Tensor dp_norms() { TORCH_CHECK(dp_on_, "dp_norms: set_dp_sgd is off"); return dp_norm_; }
+  at::Tensor dp_clip_factors() { TORCH_CHECK(dp_on_, "dp_clip_factors: set_dp_sgd is off"); return dp_c_; }
+  // the launches of DP-SGD inside train_step_clip's bf16 body
+  void dp_norm_launch(const MnistStepArgs& a, hipStream_t s) {
+    DpNormArgs d{};
+    d.data = a.data;
+    d.perm = a.perm;
+    d.step = a.step;
+    d.n = a.n_data;
+    d.B = a.B;
+    d.p1 = a.p1;
+    d.idx1 = a.idx1;
+    d.dz2 = a.dz2;
+    d.p2 = a.p2;
+    d.hd = a.hd;
+    d.dh = a.dh;
+    d.dlogits = a.dlogits;
+    d.pbf = a.pbf;
+    d.clip = (float)dp_clip_;
+    d.scale = 1;
+    d.sq = (float*)dp_sq_.data_ptr();
+    d.norm = (float*)dp_norm_.data_ptr();
+    d.c = (float*)dp_c_.data_ptr();
+    tfd::dp_norm(d, s);
+    tag("dp_norm", s);
+  }
+  void dp_noise_launch(hipStream_t s) {
+    if (!(dp_sigma_ > 0)) return;
+    DpNoiseArgs d{};
+    d.grad = (float*)grad_.data_ptr();
+    d.n = TOTAL;
+    const int64_t beg[8] = {OFF_WC1, OFF_BC1, OFF_WC2, OFF_BC2, OFF_WD1, OFF_BD1, OFF_OUT, OFF_BOUT};
+    const int64_t len[8] = {KTAPS * C1, C1, KTAPS * C1 * C2, C2, (int64_t)FEAT * HID, HID, HID * NCLS, NCLS};
+    d.nreg = 8;
+    for (int k = 0; k < 8; ++k) {
+      d.beg[k] = beg[k];
+      d.end[k] = beg[k] + len[k];
+    }
+    d.amp = (float)(dp_sigma_ * dp_clip_ / (double)B_);
+    d.step = (const int64_t*)step_.data_ptr();  // behind the bump: the draws of update global_step
+    d.seed = seed_;
+    tfd::dp_noise(d, s);
+    tag("dp_noise", s);
+  }
   void set_keep_prob(double kp) { keep_prob_ = kp; }
   void sync_shadow() {
     cast_f32_bf16((const float*)params_.data_ptr(), (uint16_t*)pbf_.data_ptr(), TOTAL, stream());
@@ -646,6 +740,8 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(dt == "bf16" || dt == "fp32", "dtype must be bf16 or fp32");
     TORCH_CHECK(dt == "bf16" || !adv_on_, "set_dtype('fp32') with set_adversarial on: the input-gradient kernel reads the "
                 "bf16 step's operands; set_adversarial(0, -1) first");
+    TORCH_CHECK(dt == "bf16" || !dp_on_, "set_dtype('fp32') with set_dp_sgd on: the per-example norm kernel reads the bf16 "
+                "step's factors; set_dp_sgd(0, 0) first");
     const bool f = dt == "fp32";
     if (f && !f1_.defined()) {
       auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device_);
@@ -749,6 +845,8 @@ class MnistEngine : public torch::CustomClassHolder {
   }
   // fp32 mode: backward_a runs the whole backward (fc + conv), backward_b the slab reduce
   void backward_a() {
+    TORCH_CHECK(!dp_on_, "backward_a: set_dp_sgd is on and the step pieces neither clip nor add noise: the gradient they "
+                "leave is not private; train with train_step or a captured step, or set_dp_sgd(0, 0) first");
     if (fp32_) mnist_f32_backward(args_f32(), stream());
     else mnist_backward_a(args(), stream());
   }
@@ -839,6 +937,10 @@ class MnistEngine : public torch::CustomClassHolder {
     TORCH_CHECK(!(adv_on_ && (zero_ || sfb_active())), "set_adversarial conflicts with ", zero_ ? "ZeRO-1 (set_zero)" :
                 "sufficient-factor fc gradients (set_fc_sfb)", ": the pre-pass needs whole parameters and buffers of its "
                 "own on every rank; use the all-reduce schedule");
+    // set_dp_sgd refuses these at set-up; they may have been switched on after it
+    TORCH_CHECK(!(dp_on_ && (zero_ || sfb_active() || dp())), "set_dp_sgd conflicts with ", zero_ ? "ZeRO-1 (set_zero)" :
+                sfb_active() ? "sufficient-factor fc gradients (set_fc_sfb)" : "more than one worker",
+                ": the noise is added once to the whole gradient of one GPU; multi-rank DP-SGD is not built");
     // one launch over the whole buffer: a shard or a bucket may cut a 256-element block
     TORCH_CHECK(!(opt_ == OptKind::Adam8 && (zero_ || sfb_active())), "set_adam8 conflicts with ",
                 zero_ ? "ZeRO-1 (set_zero)" : "sufficient-factor fc gradients (set_fc_sfb)",
@@ -856,7 +958,7 @@ class MnistEngine : public torch::CustomClassHolder {
       train_step_accum(dp);
       return;
     }
-    if (clip_norm_ > 0 || layerwise() || guard_ || (dp && opt_ == OptKind::Adam8)) {
+    if (clip_norm_ > 0 || layerwise() || guard_ || dp_on_ || (dp && opt_ == OptKind::Adam8)) {
       train_step_clip(dp);
       return;
     }
@@ -1176,7 +1278,14 @@ class MnistEngine : public torch::CustomClassHolder {
       tag("fc_fwd", s);
       log_loss(a.step, SL_WHOLE, s);
       mark(P_FWD, s);
-      mnist_backward_a(a, s, 0);
+      if (dp_on_) {  // DP-SGD: dz2 first, the per-example norms and the row scaling, then the weight gradients
+        mnist_backward_a(a, s, 2);
+        tag("fc1_dx", s);
+        dp_norm_launch(a, s);
+        mnist_backward_a(a, s, 1);
+      } else {
+        mnist_backward_a(a, s, 0);
+      }
       tag("fc_bwd", s);
       mark(P_BFC, s);
       if (dp) {
@@ -1190,6 +1299,7 @@ class MnistEngine : public torch::CustomClassHolder {
       tag("conv_bwd", s);
       mnist_conv_grad_reduce(a, s);
       tag("slab_reduce", s);
+      if (dp_on_) dp_noise_launch(s);
       if (dp) {
         all_reduce_conv(s, bf);  // behind bucket A's on the comm stream: ev_done_ covers both
         wait(s, ev_done_, "grad_norm<-ar_conv");
@@ -2268,6 +2378,10 @@ class MnistEngine : public torch::CustomClassHolder {
   // FGSM adversarial training (set_adversarial): on, {eps, adv_rows}, the perturbed batch the step kernels
   // read as fed rows, and the loss / accuracy rows of the pre-pass's own head
   bool adv_on_ = false;
+  // DP-SGD (set_dp_sgd): on, the clip bound C, the noise multiplier sigma; the last step's sq [B][8], norm [B], c [B]
+  bool dp_on_ = false;
+  double dp_clip_ = 0.0, dp_sigma_ = 0.0;
+  at::Tensor dp_sq_, dp_norm_, dp_c_;
   std::vector<double> adv_user_ = {0.0, -1.0};
   at::Tensor xadv_, yadv_, adv_loss_, adv_correct_;
   at::Tensor f1_, f2_, fhd_, fdh_, fdz2_, fslab_, fwg2_;  // fp32-mode activations / slabs
@@ -2386,6 +2500,10 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("fgsm", &MnistEngine::fgsm, "", {torch::arg("x"), torch::arg("y"), torch::arg("eps"), torch::arg("adv_rows") = -1})
       .def("set_adversarial", &MnistEngine::set_adversarial, "", {torch::arg("eps"), torch::arg("adv_rows") = -1})
       .def("adversarial", &MnistEngine::adversarial)
+      .def("set_dp_sgd", &MnistEngine::set_dp_sgd, "", {torch::arg("l2_norm_clip"), torch::arg("noise_multiplier") = 0.0})
+      .def("dp_sgd", &MnistEngine::dp_sgd)
+      .def("dp_norms", &MnistEngine::dp_norms)
+      .def("dp_clip_factors", &MnistEngine::dp_clip_factors)
       .def("set_keep_prob", &MnistEngine::set_keep_prob)
       .def("sync_shadow", &MnistEngine::sync_shadow)
       .def("set_adam", &MnistEngine::set_adam)

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --dp_l2_norm_clip --dp_noise_multiplier --dp_delta --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -102,6 +102,13 @@ def main(argv=None):
                     "perturbed (batch_size / 2: the half-clean batch of Kurakin et al.); -1 = all")
     ap.add_argument("--adv_eval_eps", type=float, default=0.0, help="also print the accuracy of the final evaluation's "
                     "rows under FGSM at this eps (Adversarial Testing Accuracy); 0 = off")
+    ap.add_argument("--dp_l2_norm_clip", type=float, default=0.0, help="DP-SGD: clip every example's gradient to this L2 "
+                    "norm before the sum (GPU: per-example norms from one launch inside the step graph, csrc/mnist_dp.h; "
+                    "CPU: per-example fp64 autograd); 0 = off")
+    ap.add_argument("--dp_noise_multiplier", type=float, default=0.0, help="--dp_l2_norm_clip: add N(0, (this x clip)^2) "
+                    "to the clipped sum before the average")
+    ap.add_argument("--dp_delta", type=float, default=1e-5, help="--dp_l2_norm_clip: the delta of the reported epsilon "
+                    "(training/privacy.py; Poisson sampling assumed)")
     ap.add_argument("--device_eval", action="store_true", help="upload the validation split once and evaluate it on "
                     "the device: the --eval_batches x 100 rows in split order (not next_batch's shuffle: the same mean "
                     "whenever they are the whole split, as the default 50 x 100 are), one record per batch folded by the "
@@ -140,6 +147,16 @@ def main(argv=None):
         ap.error("--adv_eps with --grad_accum_steps > 1: the adversarial pre-pass perturbs one batch, not K micro-batches")
     if (a.adv_eps > 0 or a.adv_eval_eps > 0) and a.dtype == "fp32" and not a.cpu and torch.cuda.is_available():
         ap.error("--adv_eps / --adv_eval_eps with --dtype fp32: the input-gradient kernel reads the bf16 step's operands")
+    if a.dp_l2_norm_clip < 0 or a.dp_noise_multiplier < 0 or not 0 < a.dp_delta < 1:
+        ap.error("--dp_l2_norm_clip and --dp_noise_multiplier must be >= 0, --dp_delta in (0, 1)")
+    if a.dp_noise_multiplier > 0 and a.dp_l2_norm_clip == 0:
+        ap.error("--dp_noise_multiplier needs --dp_l2_norm_clip: the noise has no scale without the bound")
+    if a.dp_l2_norm_clip > 0 and a.grad_accum_steps > 1:
+        ap.error("--dp_l2_norm_clip with --grad_accum_steps > 1: the noise is added once per update")
+    if a.dp_l2_norm_clip > 0 and a.adv_eps > 0:
+        ap.error("--dp_l2_norm_clip with --adv_eps: the privacy analysis covers each example's own row")
+    if a.dp_l2_norm_clip > 0 and a.dtype == "fp32" and not a.cpu and torch.cuda.is_available():
+        ap.error("--dp_l2_norm_clip with --dtype fp32: the per-example norm kernel reads the bf16 step's factors")
     step_rows = a.batch_size * a.grad_accum_steps  # images per optimizer step
 
     # Import MNIST data (mnist_single.py:14-15)
@@ -180,6 +197,8 @@ def main(argv=None):
         runner.set_augment(*augment)
     if a.adv_eps > 0:
         runner.set_adversarial(a.adv_eps, a.adv_rows)
+    if a.dp_l2_norm_clip > 0:
+        runner.set_dp_sgd(a.dp_l2_norm_clip, a.dp_noise_multiplier)
 
     start_time = time.time()
     train_flag = a.train_flag
@@ -227,6 +246,12 @@ def main(argv=None):
                 step - 1, a.grad_accum_steps, a.batch_size, (step - 1) * step_rows / max(training_end_time - start_time, 1e-9)))
         if a.skip_nonfinite and runner.skipped_steps() > 0:
             print("--skip_nonfinite skipped %d of %d optimizer steps (gradient not finite)" % (runner.skipped_steps(), step - 1))
+        if a.dp_l2_norm_clip > 0:
+            from tensorflow_distributed_amd.training.privacy import epsilon
+            q = a.batch_size / float(mnist.train.num_examples)
+            print("DP-SGD: clip %g, noise multiplier %g, %d steps at q = %.5f: epsilon = %.3f at delta = %g (Poisson sampling "
+                  "assumed); last step clipped %.0f%% of its rows" % (a.dp_l2_norm_clip, a.dp_noise_multiplier, step - 1, q,
+                  epsilon(q, a.dp_noise_multiplier, step - 1, a.dp_delta), a.dp_delta, 100 * runner.dp_clipped_fraction()))
         if a.logdir:
             print("Saved %s" % saver.save(a.logdir, runner.state_dict_tf(), global_step=runner.global_step()))
     else:

@@ -227,6 +227,8 @@ class TorchMnistRunner(MnistRunnerBase):
         self._seed, self._rank = int(seed), int(rank)
         self._aug = None    # augmentation config (set_augment), None = off
         self._adv = (0.0, -1)  # FGSM adversarial training (set_adversarial): (eps, adv_rows), eps 0 = off
+        self._dp = (0.0, 0.0)  # DP-SGD (set_dp_sgd): (l2_norm_clip, noise_multiplier), clip 0 = off
+        self.dp_last = None    # the last DP-SGD step's (norms [B], clip factors [B])
 
     def params(self) -> torch.Tensor:
         return self.flat
@@ -295,7 +297,16 @@ class TorchMnistRunner(MnistRunnerBase):
             if self.keep_prob < 1.0 else None
         logits = self._forward(x, self.keep_prob, mask)
         loss = F.cross_entropy(logits, y.long())
-        g, = torch.autograd.grad(loss, self.flat)
+        if self._dp[0] > 0:  # training/dp_sgd.py: per-example fp64 autograd, the device's noise draws
+            from ..training.dp_sgd import dp_sgd_gradient_ref
+
+            self.flat.requires_grad_(False)
+            gd, norms, c = dp_sgd_gradient_ref(self.flat, x.cpu().numpy(), y.cpu().numpy(), self._dp[0], self._dp[1],
+                                               self._step + 1, self._seed, self.keep_prob,
+                                               None if mask is None else mask.cpu().numpy())
+            g, self.dp_last = torch.from_numpy(gd).float().to(self.device), (norms, c)
+        else:
+            g, = torch.autograd.grad(loss, self.flat)
         self.flat.requires_grad_(False)
         self.grad.copy_(g)
         self._last_loss = float(loss.item())
@@ -372,6 +383,24 @@ class TorchMnistRunner(MnistRunnerBase):
         if eps > 0 and self.accum_steps > 1:
             raise ValueError("set_adversarial with accum_steps > 1: the pre-pass perturbs one batch, not K micro-batches")
         self._adv = (float(eps), int(adv_rows)) if eps > 0 else (0.0, -1)
+
+    def set_dp_sgd(self, l2_norm_clip: float = 0.0, noise_multiplier: float = 0.0) -> None:
+        """DP-SGD: every ``train_step`` clips each example's gradient to ``l2_norm_clip``, sums, adds
+        ``N(0, (noise_multiplier * l2_norm_clip)^2)`` and averages (``training/dp_sgd.py``). ``l2_norm_clip = 0``
+        turns it off. Refuses what the device engine refuses: accumulation, FGSM, more than one worker."""
+        if l2_norm_clip > 0 and self.accum_steps > 1:
+            raise ValueError("set_dp_sgd with accum_steps > 1: the noise is added once per update")
+        if l2_norm_clip > 0 and self._adv[0] > 0:
+            raise ValueError("set_dp_sgd with set_adversarial on: the analysis covers each example's own row")
+        if l2_norm_clip > 0 and self.comm is not None and getattr(self.comm, "world", 2) > 1:  # a world of 1 reduces nothing
+            raise ValueError("set_dp_sgd with more than one worker: the noise must be added once, behind the reduction")
+        if l2_norm_clip <= 0 and noise_multiplier > 0:
+            raise ValueError("set_dp_sgd: noise without a clip bound has no scale")
+        self._dp = (float(l2_norm_clip), float(noise_multiplier)) if l2_norm_clip > 0 else (0.0, 0.0)
+
+    def dp_clipped_fraction(self) -> float:
+        """the share of the last step's rows whose gradient was clipped"""
+        return float((self.dp_last[1] < 1.0).mean()) if self.dp_last is not None else 0.0
 
     # ---- step log: the device runner's three methods over a plain Python ring ----
     def set_step_log(self, capacity: int = 1024) -> None:
@@ -655,6 +684,27 @@ class NativeMnistRunner(MnistRunnerBase):
 
     def adversarial(self) -> dict:
         return dict(zip(("eps", "adv_rows"), self.eng.adversarial()))
+
+    def set_dp_sgd(self, l2_norm_clip: float = 0.0, noise_multiplier: float = 0.0) -> None:
+        """DP-SGD inside the step graph (csrc/mnist_dp.h): per-example norms and clip factors from one launch
+        between the two halves of the fc backward, the Gaussian noise from one flat pass behind the conv-gradient
+        reduce. ``l2_norm_clip = 0`` turns it off. bf16 engine, one GPU, no accumulation, no FGSM; the captured
+        graphs are dropped."""
+        self.stream.synchronize()  # the engine drops its graphs: none may still be running
+        with torch.cuda.stream(self.stream):
+            self.eng.set_dp_sgd(float(l2_norm_clip), float(noise_multiplier))
+        self._stale_graphs()
+        self._grads_graph = False
+
+    def dp_sgd(self) -> dict:
+        return dict(zip(("l2_norm_clip", "noise_multiplier"), self.eng.dp_sgd()))
+
+    def dp_clipped_fraction(self) -> float:
+        """the share of the last step's rows whose gradient was clipped"""
+        if self.eng.dp_sgd()[0] <= 0:
+            return 0.0
+        self.stream.synchronize()
+        return float((self.eng.dp_clip_factors() < 1.0).float().mean().item())
 
     def read_step_log(self, first_t: int, last_t: int) -> list:
         """The records of optimizer steps ``first_t..last_t`` (``t`` = global_step after the step) as dicts
@@ -966,6 +1016,9 @@ class NativeMnistRunner(MnistRunnerBase):
         ``accum_steps > 1`` it raises (the parameter-server modes that use it do not accumulate)."""
         if self.accum_steps > 1:
             raise ValueError(f"compute_grads handles one batch; the optimizer has accum_steps={self.accum_steps}")
+        if self.eng.dp_sgd()[0] > 0:  # the step pieces neither clip nor add noise (the engine's backward_a refuses too)
+            raise ValueError("compute_grads with set_dp_sgd on: the piecewise backward returns the unclipped, noise-free "
+                             "gradient; train with train_step / train_steps")
         self._feed(x, y)
         with torch.cuda.stream(self.stream):
             if self.use_graph:

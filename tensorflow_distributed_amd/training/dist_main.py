@@ -216,6 +216,12 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                    "(csrc/mnist_input_grad.h); CPU: fp64 autograd (training/adversarial.py). 0 = off")
     f.DEFINE_integer("adv_rows", -1, "--adv_eps: only the first this many rows of a worker's batch are perturbed "
                      "(batch_size / 2: the half-clean batch of Kurakin et al.); -1 = all")
+    f.DEFINE_float("dp_l2_norm_clip", 0.0, "DP-SGD (--model mnist_cnn, one worker): clip every example's gradient to this L2 "
+                   "norm before the sum (GPU: per-example norms from one launch inside the step graph, csrc/mnist_dp.h; CPU: "
+                   "per-example fp64 autograd); 0 = off")
+    f.DEFINE_float("dp_noise_multiplier", 0.0, "--dp_l2_norm_clip: add N(0, (this x clip)^2) to the clipped sum before the average")
+    f.DEFINE_float("dp_delta", 1e-5, "--dp_l2_norm_clip: the delta of the reported epsilon (training/privacy.py; Poisson "
+                   "sampling assumed)")
     f.DEFINE_float("adv_eval_eps", 0.0, "Also print, after the final evaluation, the accuracy of the same rows under FGSM "
                    "at this eps (Adversarial Testing Accuracy); 0 = off")
 
@@ -453,6 +459,30 @@ def check_adversarial_flags(num_workers: int) -> bool:
             raise ValueError("--adv_eps with --dp_schedule %s: the pre-pass needs whole parameters and buffers of its own on "
                              "every rank; use --dp_schedule allreduce" % FLAGS.dp_schedule)
     return FLAGS.adv_eps > 0
+
+
+def check_dp_sgd_flags(num_workers: int) -> bool:
+    """Whether --dp_l2_norm_clip turns DP-SGD on. What it does not cover is a flag error, raised before any process
+    group is built (every rank sees the same flags)."""
+    if FLAGS.dp_l2_norm_clip < 0 or FLAGS.dp_noise_multiplier < 0 or not 0 < FLAGS.dp_delta < 1:
+        raise ValueError("--dp_l2_norm_clip and --dp_noise_multiplier must be >= 0, --dp_delta in (0, 1)")
+    if FLAGS.dp_noise_multiplier > 0 and FLAGS.dp_l2_norm_clip == 0:
+        raise ValueError("--dp_noise_multiplier needs --dp_l2_norm_clip: the noise has no scale without the bound")
+    if not FLAGS.dp_l2_norm_clip > 0:
+        return False
+    which = "--dp_l2_norm_clip"
+    if num_workers > 1 or bool(FLAGS.ps_hosts) or not FLAGS.sync_replicas:
+        raise ValueError("%s with more than one worker or a parameter-server mode: the noise must be added once, behind the "
+                         "reduction of the clipped sums, which no schedule here does; run one worker" % which)
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("%s with --model %s: the per-example norm kernel is the MNIST CNN's" % (which, FLAGS.model))
+    if FLAGS.num_gpus > 0 and FLAGS.dtype == "fp32":
+        raise ValueError("%s with --dtype fp32: the per-example norm kernel reads the bf16 step's factors" % which)
+    if FLAGS.grad_accum_steps > 1:
+        raise ValueError("%s with --grad_accum_steps > 1: the noise is added once per update" % which)
+    if FLAGS.adv_eps > 0:
+        raise ValueError("%s with --adv_eps: the privacy analysis covers each example's own row" % which)
+    return True
 
 
 def check_steps_per_call_flags(num_workers: int) -> None:
@@ -947,6 +977,7 @@ def main(argv=None) -> int:
     check_steps_per_call_flags(len(FLAGS.worker_hosts.split(",")))
     check_augment_flags(len(FLAGS.worker_hosts.split(",")))
     check_adversarial_flags(len(FLAGS.worker_hosts.split(",")))
+    check_dp_sgd_flags(len(FLAGS.worker_hosts.split(",")))
     check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
@@ -1043,6 +1074,13 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         runner.set_augment(*augment_flags())
     if check_adversarial_flags(num_workers):
         runner.set_adversarial(FLAGS.adv_eps, FLAGS.adv_rows)
+    dp_sgd_on = check_dp_sgd_flags(num_workers)
+    if dp_sgd_on:
+        from .privacy import epsilon_from_rdp, rdp_per_step
+        runner.set_dp_sgd(FLAGS.dp_l2_norm_clip, FLAGS.dp_noise_multiplier)
+        dp_q = FLAGS.batch_size / float(mnist.train.num_examples)
+        dp_rdp = rdp_per_step(dp_q, FLAGS.dp_noise_multiplier)  # once: a step's epsilon is then one pass over the orders
+        dp_epsilon_at = lambda n: epsilon_from_rdp(dp_rdp, n, FLAGS.dp_delta)
 
     sv = _prepare_session(cluster, is_chief, runner,
                           lambda: runner.load_flat(M.flat_from_dict(M.init_params(FLAGS.seed)), {}, 0), gsync.broadcast)
@@ -1181,6 +1219,10 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                     rec["ema_decay"] = ema_decay_at(opt.ema_decay, r["step"], opt.ema_num_updates)
                 if augment:
                     rec["augment"] = list(augment_flags())
+                if dp_sgd_on:  # epsilon after this step; the clip factors on the device are the call's last step's
+                    rec["dp_epsilon"] = dp_epsilon_at(local_step)
+                    if last:
+                        rec["dp_clipped_fraction"] = runner.dp_clipped_fraction()
                 if last and phase_timing:
                     ph = runner.phase_times()
                     rec.update(ph)
@@ -1224,6 +1266,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                 rec["ema_decay"] = ema_decay_at(opt.ema_decay, step, opt.ema_num_updates)
             if augment:
                 rec["augment"] = list(augment_flags())
+            if dp_sgd_on:
+                rec["dp_epsilon"], rec["dp_clipped_fraction"] = dp_epsilon_at(local_step), runner.dp_clipped_fraction()
             if phase_timing:
                 ph = runner.phase_times()
                 rec.update(ph)
@@ -1270,8 +1314,15 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
     if skipped > 0:
         print("Worker %d: --skip_nonfinite skipped %d of %d optimizer steps (aggregated gradient not finite)"
               % (FLAGS.task_index, skipped, local_step))
+    dp_final = {}
+    if dp_sgd_on:
+        q = dp_q
+        dp_final = dict(dp_clipped_fraction=runner.dp_clipped_fraction(), dp_epsilon=dp_epsilon_at(local_step))
+        print("DP-SGD: clip %g, noise multiplier %g, %d steps at q = %.5f: epsilon = %.3f at delta = %g (Poisson sampling "
+              "assumed); last step clipped %.0f%% of its rows" % (FLAGS.dp_l2_norm_clip, FLAGS.dp_noise_multiplier, local_step, q,
+              dp_final["dp_epsilon"], FLAGS.dp_delta, 100 * dp_final["dp_clipped_fraction"]))
     metrics.log(event="final", global_step=step, training_time_s=training_time, mean_accuracy=mean_accuracy,
-                **({"skipped_steps": skipped} if opt.skip_nonfinite else {}))
+                **({"skipped_steps": skipped} if opt.skip_nonfinite else {}), **dp_final)
     if perf_rows:
         print(performance_table(perf_rows), end="")
     metrics.close()
