@@ -28,6 +28,7 @@
 #include "../mnist_dp.h"
 #include "../mnist_input_grad.h"
 #include "../mnist_infer.h"
+#include "../mnist_mc.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
 #include "../optim_q8.h"
@@ -1567,6 +1568,68 @@ class MnistEngine : public torch::CustomClassHolder {
     return {logits, classes, loss, correct};
   }
 
+  // Monte-Carlo dropout (csrc/mnist_mc.h): predict's forward, then `samples` masked passes of the output layer per
+  // row in one launch per chunk. Row i of x draws as global row row0 + i, so the results depend neither on the
+  // chunking nor on B. keep_prob <= 0: the engine's own. Returns (mean_prob [n,10], classes [n] int32, entropy [n],
+  // mutual_info [n], var_prob [n,10], loss_rows [n], correct_rows [n]); the last two are empty without labels.
+  // Observation only: it writes buffers of its own, as predict does.
+  std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> predict_mc(
+      at::Tensor x, at::Tensor y, int64_t samples, double keep_prob, int64_t seed, bool use_ema, int64_t row0) {
+    check_rows("predict_mc: x", x, at::kFloat, 2);
+    TORCH_CHECK(x.size(1) == 784, "predict_mc: x must be [n,784], got [", x.size(0), ",", x.size(1), "]");
+    const int64_t n = x.size(0);
+    const bool labelled = y.numel() > 0;
+    if (labelled) {
+      check_rows("predict_mc: y", y, at::kInt, 1);
+      TORCH_CHECK(y.size(0) == n, "predict_mc: y has ", y.size(0), " labels for ", n, " rows");
+    }
+    TORCH_CHECK(samples >= 1 && samples <= kMcMaxSamples, "predict_mc: 1 <= samples <= ", kMcMaxSamples, ", got ", samples);
+    const double kp = keep_prob <= 0 ? keep_prob_ : keep_prob;
+    TORCH_CHECK(kp > 0 && kp <= 1, "predict_mc: 0 < keep_prob <= 1, got ", kp);
+    TORCH_CHECK(row0 >= 0, "predict_mc: row0 >= 0");
+    TORCH_CHECK(!use_ema || ema_on(), "predict_mc(use_ema): set_ema first");
+    auto mean_prob = at::empty({n, NCLS}, x.options()), var_prob = at::empty({n, NCLS}, x.options());
+    auto classes = at::empty({n}, x.options().dtype(at::kInt));
+    auto entropy = at::empty({n}, x.options()), mi = at::empty({n}, x.options());
+    auto loss = at::empty({labelled ? n : 0}, x.options()), correct = at::empty({labelled ? n : 0}, x.options());
+    if (n == 0) return {mean_prob, classes, entropy, mi, var_prob, loss, correct};
+    refresh_ema_image(use_ema, stream());
+    for (int64_t o = 0; o < n; o += B_) {
+      const int nb = (int)std::min<int64_t>(B_, n - o);
+      const InferHeadArgs h = infer_forward((const float*)x.data_ptr() + o * 784, nb, use_ema, stream());
+      McHeadArgs m{};
+      m.rows = h.rows;
+      m.fc1_slab = h.fc1_slab;
+      m.splits = h.splits;
+      m.split_rows = h.split_rows;
+      m.p32 = h.p32;
+      m.labels = labelled ? (const int*)y.data_ptr() + o : nullptr;
+      m.samples = (int)samples;
+      m.keep_prob = (float)kp;
+      m.seed = (uint32_t)seed;
+      m.rank = rank_;
+      m.row0 = (uint64_t)(row0 + o);
+      m.mean_prob = (float*)mean_prob.data_ptr() + o * NCLS;
+      m.classes = (int*)classes.data_ptr() + o;
+      m.entropy = (float*)entropy.data_ptr() + o;
+      m.mutual_info = (float*)mi.data_ptr() + o;
+      m.var_prob = (float*)var_prob.data_ptr() + o * NCLS;
+      m.loss_row = labelled ? (float*)loss.data_ptr() + o : nullptr;
+      m.correct_row = labelled ? (float*)correct.data_ptr() + o : nullptr;
+      mc_head(m, stream());
+    }
+    return {mean_prob, classes, entropy, mi, var_prob, loss, correct};
+  }
+  // A test hook, not part of the inference interface: the fc1 split-K slabs of the last inference forward (the last
+  // chunk of predict / predict_mc / evaluate_dataset), [splits, rows of that chunk, 1024] fp32, a view. The engine
+  // knows the chunk's rows and the split count itself; the view is stale after the next forward of any kind.
+  at::Tensor infer_slabs() {
+    TORCH_CHECK(infer_rows_ > 0, "infer_slabs: no inference forward has run");
+    const at::Tensor& s = fp32_ ? fslab_ : fc1_slab_;
+    const int64_t splits = fp32_ ? mnist_f32_fc1_splits() : fc1_splits_;
+    return s.view({-1}).narrow(0, 0, splits * infer_rows_ * HID).view({splits, infer_rows_, HID});
+  }
+
   // A device-resident evaluation split, uploaded once: images [N,784] fp32, labels [N] int32 in
   // [0, 10) (checked here: one synchronisation). Graphs captured over an earlier split are dropped.
   void set_eval_dataset(at::Tensor images, at::Tensor labels) {
@@ -2193,6 +2256,7 @@ class MnistEngine : public torch::CustomClassHolder {
     InferHeadArgs h{};
     h.rows = nb;
     h.split_rows = nb;
+    infer_rows_ = nb;
     h.p32 = (const float*)(use_ema ? ema_ : params_).data_ptr();
     MnistStepArgs a = args();
     a.B = nb;
@@ -2346,6 +2410,7 @@ class MnistEngine : public torch::CustomClassHolder {
   double keep_prob_;
   uint32_t seed_, rank_;
   int fc1_splits_, wg2_splits_;
+  int64_t infer_rows_ = 0;  // rows of the last inference forward (infer_slabs)
   int64_t input_mode_ = 0;
   OptKind opt_ = OptKind::Adam;
   // RMSProp / Adagrad (set_rmsprop / set_adagrad): the rule's scalars and the centered rule's third slot
@@ -2564,6 +2629,10 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
       .def("train_step", &MnistEngine::train_step)
       .def("evaluate", &MnistEngine::evaluate, "", {torch::arg("x"), torch::arg("y"), torch::arg("use_ema") = false})
       .def("predict", &MnistEngine::predict, "", {torch::arg("x"), torch::arg("y"), torch::arg("use_ema") = false})
+      .def("predict_mc", &MnistEngine::predict_mc, "",
+           {torch::arg("x"), torch::arg("y"), torch::arg("samples"), torch::arg("keep_prob"), torch::arg("seed"),
+            torch::arg("use_ema") = false, torch::arg("row0") = 0})
+      .def("infer_slabs", &MnistEngine::infer_slabs)
       .def("set_eval_dataset", &MnistEngine::set_eval_dataset)
       .def("eval_dataset_rows", &MnistEngine::eval_dataset_rows)
       .def("evaluate_dataset", &MnistEngine::evaluate_dataset, "",

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --dp_l2_norm_clip --dp_noise_multiplier --dp_delta --device_eval --confusion_matrix --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --dp_l2_norm_clip --dp_noise_multiplier --dp_delta --device_eval --confusion_matrix --mc_dropout_samples --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
-from tensorflow_distributed_amd.models.mnist_runner import make_runner  # noqa: E402
+from tensorflow_distributed_amd.models.mnist_runner import format_mc_dropout, make_runner, mc_dropout_summary  # noqa: E402
 from tensorflow_distributed_amd.training import checkpoint, inference  # noqa: E402
 from tensorflow_distributed_amd.training.augment import augment_config, augment_on  # noqa: E402
 from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
@@ -115,6 +115,10 @@ def main(argv=None):
                     "engine (GPU: one replayed graph, one read-back); off = the host-fed loop")
     ap.add_argument("--confusion_matrix", action="store_true", help="--device_eval: print the 10 x 10 confusion matrix "
                     "and the per-class recall and precision of the validation pass")
+    ap.add_argument("--mc_dropout_samples", type=int, default=0, help="Monte-Carlo dropout: after the final evaluation, "
+                    "this many dropout passes per row over the rows --device_eval evaluates (GPU: one launch per batch "
+                    "behind one forward, csrc/mnist_mc.h); prints the accuracy of the mean prediction and the mean "
+                    "predictive entropy and mutual information of the correct and the wrong rows; 0 = off")
     ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
                     "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
@@ -133,6 +137,8 @@ def main(argv=None):
             ap.error("--steps_per_call > 1 with --no_graph: the steps of a call are one captured graph")
     if a.confusion_matrix and not a.device_eval:
         ap.error("--confusion_matrix is folded by --device_eval: give both")
+    if not 0 <= a.mc_dropout_samples <= inference.MC_MAX_SAMPLES:
+        ap.error("--mc_dropout_samples must be in [0, %d] (0 = off)" % inference.MC_MAX_SAMPLES)
     augment = (a.augment_shift, a.augment_rotate, a.augment_scale, a.elastic_alpha, a.elastic_sigma)
     try:
         augment_config(*augment)
@@ -289,6 +295,10 @@ def main(argv=None):
         print("Adversarial Testing Accuracy (eps=%g) : %f" % (a.adv_eval_eps, adv_correct / float(adv_n)))
     if a.confusion_matrix:
         print(inference.format_confusion(inference.merge_records(recs)["confusion"]))
+    if a.mc_dropout_samples > 0:
+        rows = min(nt * 100, mnist.validation.num_examples)
+        res = runner.predict_mc(mnist.validation.images[:rows], None, a.mc_dropout_samples, use_ema=use_ema)
+        print(format_mc_dropout(mc_dropout_summary(res, mnist.validation.labels[:rows]), a.mc_dropout_samples, dropout))
     testing_end_time = time.time()
     print("--- %s seconds Time for Inference ---" % (testing_end_time - training_end_time))
     return 0

@@ -87,6 +87,40 @@ def _eval_range(split, first, count, group):
     return first, count, group
 
 
+MC_KEYS = ("mean_prob", "classes", "entropy", "mutual_info", "var_prob", "loss_rows", "correct_rows")  # predict_mc's results
+
+
+def _mc_args(samples, keep_prob, seed, own_keep_prob, own_seed):
+    """predict_mc's ``(keep_prob, seed)`` with the runner's own where none is given, refused as the engine refuses"""
+    if not 1 <= int(samples) <= inference.MC_MAX_SAMPLES:
+        raise ValueError(f"predict_mc: 1 <= samples <= {inference.MC_MAX_SAMPLES}, got {samples}")
+    kp = float(own_keep_prob if keep_prob is None or keep_prob <= 0 else keep_prob)
+    if not 0 < kp <= 1:
+        raise ValueError(f"predict_mc: 0 < keep_prob <= 1, got {kp}")
+    return kp, int(own_seed if seed is None else seed)
+
+
+def mc_dropout_summary(res: dict, labels) -> dict:
+    """One ``predict_mc`` result against its labels: the accuracy of the mean prediction, and the mean predictive
+    entropy and mean mutual information over the correct and over the wrong rows (NaN where there is none)."""
+    ok = res["classes"].cpu().numpy() == _labels_to_ids(labels).numpy()
+    ent, mi = res["entropy"].cpu().numpy().astype(np.float64), res["mutual_info"].cpu().numpy().astype(np.float64)
+
+    def mean(v, sel):
+        return float(v[sel].mean()) if sel.any() else float("nan")
+
+    return {"rows": int(ok.size), "correct": int(ok.sum()), "accuracy": float(ok.mean()) if ok.size else float("nan"),
+            "entropy_correct": mean(ent, ok), "entropy_wrong": mean(ent, ~ok),
+            "mutual_info_correct": mean(mi, ok), "mutual_info_wrong": mean(mi, ~ok)}
+
+
+def format_mc_dropout(s: dict, samples: int, keep_prob: float) -> str:
+    """the drivers' one line for a ``mc_dropout_summary``"""
+    return ("MC-dropout Testing Accuracy (T=%d, keep_prob=%g) : %f; predictive entropy correct %.4f / wrong %.4f; "
+            "mutual information correct %.4f / wrong %.4f" % (samples, keep_prob, s["accuracy"], s["entropy_correct"],
+                                                              s["entropy_wrong"], s["mutual_info_correct"], s["mutual_info_wrong"]))
+
+
 class MnistRunnerBase:
     batch_size: int
     device: torch.device
@@ -500,6 +534,33 @@ class TorchMnistRunner(MnistRunnerBase):
             torch.zeros(0, dtype=torch.int32)
         return logits, classes.to(self.device)
 
+    @torch.no_grad()
+    def predict_mc(self, x, y=None, samples: int = 20, keep_prob: Optional[float] = None, seed: Optional[int] = None,
+                   use_ema: bool = False, row0: int = 0) -> dict:
+        """Monte-Carlo dropout by the fp64 definition (``inference.mc_dropout_ref``) over the fp32 forward up to
+        fc1, with the masks the device draws (``inference.mc_dropout_masks``). See ``NativeMnistRunner.predict_mc``."""
+        kp, seed = _mc_args(samples, keep_prob, seed, self.keep_prob, self._seed)
+        x = _as_rows(x).to(self.device)
+        p = M.dict_from_flat(self.ema_params() if use_ema else self.flat)
+        ys = None if y is None else _labels_to_ids(y).numpy()
+        # rows x samples per chunk is bounded: the fp64 masks and masked activations are [rows, samples, 1024] each
+        chunk = max(1, min(self._PREDICT_CHUNK, 4096 // int(samples)))
+        parts = []
+        for o in range(0, x.shape[0], chunk):
+            a = x[o:o + chunk].reshape(-1, M.IMG, M.IMG, 1)
+            a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc1"], p["bc1"])), 2)
+            a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc2"], p["bc2"])), 2)
+            h = a.reshape(-1, M.FEAT) @ p["wd1"] + p["bd1"]
+            masks = inference.mc_dropout_masks(h.shape[0], samples, row0 + o, self._rank, seed, kp)
+            parts.append(inference.mc_dropout_ref(h.cpu().numpy(), p["out"].cpu().numpy(), p["out_b"].cpu().numpy(), masks, kp,
+                                                  None if ys is None else ys[o:o + chunk]))
+        out = {}
+        for k in MC_KEYS:
+            dt, tail = (np.int32 if k == "classes" else np.float32), ((M.NCLS,) if k.endswith("_prob") else ())
+            rows = [r[k] for r in parts if k in r]
+            out[k] = torch.from_numpy(np.concatenate(rows).astype(dt) if rows else np.zeros((0,) + tail, dt))
+        return out
+
     def set_eval_dataset(self, images, labels) -> None:
         """Keep an evaluation split for ``evaluate_dataset``; labels outside [0, 10) are refused."""
         self._eval_x, self._eval_y = _check_eval_split(images, labels)
@@ -532,6 +593,7 @@ class NativeMnistRunner(MnistRunnerBase):
         self.opt = base_optimizer(optimizer)
         self.eng = torch.classes.tfd.MnistEngine(batch_size, self.device.index, keep_prob, seed, rank)
         self.eng.set_dtype(dtype)  # "bf16" MFMA operands, or "fp32" (the reference's precision)
+        self._seed = int(seed)
         o = self.opt
         lr0 = lr_at(o.learning_rate, 0)
         if o.kind == "adam":
@@ -1084,6 +1146,22 @@ class NativeMnistRunner(MnistRunnerBase):
             logits, classes, _, _ = self.eng.predict(x, none, bool(use_ema))
         self.stream.synchronize()
         return logits, classes
+
+    def predict_mc(self, x, y=None, samples: int = 20, keep_prob: Optional[float] = None, seed: Optional[int] = None,
+                   use_ema: bool = False, row0: int = 0) -> dict:
+        """Monte-Carlo dropout on the device (csrc/mnist_mc.h): ``samples`` dropout passes of the output layer per
+        row behind ONE forward, one launch per chunk of the engine's batch. Returns ``{mean_prob [n,10], classes [n]
+        int32 (first maximum of mean_prob), entropy [n] (of the mean), mutual_info [n] (BALD), var_prob [n,10],
+        loss_rows [n] (-log mean_prob[label]), correct_rows [n]}``; the last two are empty without ``y``. ``keep_prob``
+        and ``seed`` default to the runner's; row ``i`` draws as global row ``row0 + i``, so the result depends
+        neither on the chunking nor on the batch size. Observation only: no training state changes."""
+        kp, seed = _mc_args(samples, keep_prob, seed, self.keep_prob, self._seed)
+        x = _as_rows(x).to(self.device).contiguous()
+        yd = torch.empty(0, dtype=torch.int32, device=self.device) if y is None else _labels_to_ids(y).to(self.device).contiguous()
+        with torch.cuda.stream(self.stream):
+            out = self.eng.predict_mc(x, yd, int(samples), kp, seed, bool(use_ema), int(row0))
+        self.stream.synchronize()
+        return dict(zip(MC_KEYS, out))
 
     def set_eval_dataset(self, images, labels) -> None:
         """Upload an evaluation split once; ``evaluate_dataset`` reads it on the device. Labels outside

@@ -2,6 +2,7 @@
 
     python -m tensorflow_distributed_amd.predict --logdir DIR [--split validation|test|train] [--use_ema]
         [--dtype bf16|fp32] [--out FILE.npz] [--confusion_matrix] [--data_dir DIR] [--rows N] [--batch_size N] [--cpu]
+        [--mc_dropout_samples T] [--keep_prob P]
 
 Restores the latest checkpoint under ``--logdir`` (mnist_single.py --logdir, dist_main's Supervisor),
 runs the forward over one split of the data set -- on a GPU through the native engine's inference head
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from .models import mnist_cnn as M
-from .models.mnist_runner import EMA_SUFFIX, make_runner
+from .models.mnist_runner import EMA_SUFFIX, format_mc_dropout, make_runner, mc_dropout_summary
 from .training import checkpoint, inference
 from .training.optimizers import AdamOptimizer
 from .utils import input_data
@@ -40,9 +41,16 @@ def main(argv=None) -> int:
     ap.add_argument("--rows", type=int, default=0, help="only the first N rows of the split (0 = all of it)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the synthetic data set when no IDX files exist")
     ap.add_argument("--cpu", action="store_true", help="force the fp32 PyTorch CPU path")
+    ap.add_argument("--mc_dropout_samples", type=int, default=0, help="Monte-Carlo dropout: this many dropout passes per "
+                    "row at --keep_prob; prints the accuracy of the mean prediction with the mean predictive entropy and "
+                    "mutual information of the correct and the wrong rows, and adds mean_prob, entropy, mutual_info and "
+                    "var_prob to --out; 0 = off")
+    ap.add_argument("--keep_prob", type=float, default=0.75, help="--mc_dropout_samples: the dropout keep probability")
     a = ap.parse_args(argv)
     if a.batch_size < 1:
         ap.error("--batch_size must be >= 1")
+    if not 0 <= a.mc_dropout_samples <= inference.MC_MAX_SAMPLES or not 0 < a.keep_prob <= 1:
+        ap.error("--mc_dropout_samples must be in [0, %d] (0 = off), --keep_prob in (0, 1]" % inference.MC_MAX_SAMPLES)
     latest = checkpoint.latest_checkpoint(a.logdir)
     if not latest:
         ap.error("--logdir %s holds no checkpoint" % a.logdir)
@@ -71,10 +79,15 @@ def main(argv=None) -> int:
     print("Mean loss : %f" % (whole["loss_sum"] / float(max(n, 1))))
     if a.confusion_matrix:
         print(inference.format_confusion(whole["confusion"]))
+    mc = {}
+    if a.mc_dropout_samples > 0:
+        res = runner.predict_mc(images, None, a.mc_dropout_samples, a.keep_prob, use_ema=a.use_ema)
+        print(format_mc_dropout(mc_dropout_summary(res, labels), a.mc_dropout_samples, a.keep_prob))
+        mc = {k: res[k].cpu().numpy() for k in ("mean_prob", "entropy", "mutual_info", "var_prob")}
     if a.out:
         logits, classes = runner.predict(images, use_ema=a.use_ema)
         np.savez(a.out, logits=logits.cpu().numpy().astype(np.float32), classes=classes.cpu().numpy().astype(np.int32),
-                 labels=labels)
+                 labels=labels, **mc)
         print("Wrote %s" % a.out)
     return 0
 

@@ -147,6 +147,11 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "one replayed graph, one read-back). --model mnist_cnn, synchronous all-reduce training")
     f.DEFINE_boolean("confusion_matrix", False, "--device_eval: print the 10 x 10 confusion matrix and the per-class "
                      "recall and precision of the final pass; the metrics file's evaluation record carries them")
+    f.DEFINE_integer("mc_dropout_samples", 0, "Monte-Carlo dropout: after the final evaluation, this many dropout passes "
+                     "per row over the rows --device_eval evaluates (GPU: one launch per batch behind one forward, "
+                     "csrc/mnist_mc.h); prints MC-dropout Testing Accuracy with the mean predictive entropy and mutual "
+                     "information of the correct and the wrong rows, and logs an mc_dropout record. --model mnist_cnn, "
+                     "synchronous all-reduce training; 0 = off")
     f.DEFINE_string("metrics_file", "", "Chief: JSONL metrics per step")
     f.DEFINE_string("trace_file", "", "Chrome-trace JSON of host step phases")
     f.DEFINE_integer("check_consistency_every", 0, "Every N steps all-reduce a param checksum and "
@@ -530,6 +535,25 @@ def check_device_eval_flags(num_workers: int) -> None:
                          "fetched step by step; evaluate those runs with the host-fed pass")
     if FLAGS.eval_batches < 1 or FLAGS.eval_batch_size < 1:
         raise ValueError("--device_eval: --eval_batches and --eval_batch_size must be >= 1")
+
+
+def check_mc_dropout_flags(num_workers: int) -> None:
+    """--mc_dropout_samples runs on the worker's engine, where --device_eval does; it refuses what that refuses."""
+    if FLAGS.mc_dropout_samples == 0:
+        return
+    from .inference import MC_MAX_SAMPLES
+
+    if not 1 <= FLAGS.mc_dropout_samples <= MC_MAX_SAMPLES:
+        raise ValueError("--mc_dropout_samples must be in [0, %d] (0 = off)" % MC_MAX_SAMPLES)
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--mc_dropout_samples with --model %s: the ResNet has no dropout layer to sample" % FLAGS.model)
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts)):
+        raise ValueError("--mc_dropout_samples in the parameter-server role (--sync_replicas=False, or backup workers "
+                         "with --ps_hosts): the variables live on the ps tasks; sample a checkpoint of such a run with "
+                         "python -m tensorflow_distributed_amd.predict --mc_dropout_samples")
+    if FLAGS.eval_batches < 1 or FLAGS.eval_batch_size < 1:
+        raise ValueError("--mc_dropout_samples: --eval_batches and --eval_batch_size must be >= 1")
 
 
 def check_ema_flags(num_workers: int) -> None:
@@ -979,6 +1003,7 @@ def main(argv=None) -> int:
     check_adversarial_flags(len(FLAGS.worker_hosts.split(",")))
     check_dp_sgd_flags(len(FLAGS.worker_hosts.split(",")))
     check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
+    check_mc_dropout_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -1310,6 +1335,14 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                         adv_accuracy=adv_eval["correct"] / float(max(adv_eval["rows"], 1)), adv_eps=FLAGS.adv_eval_eps)
     if adv_eval["on"]:
         print("Adversarial Testing Accuracy (eps=%g) : %f" % (FLAGS.adv_eval_eps, adv_eval["correct"] / float(max(adv_eval["rows"], 1))))
+    if FLAGS.mc_dropout_samples > 0:
+        from ..models.mnist_runner import format_mc_dropout, mc_dropout_summary
+
+        mc = mc_dropout_summary(runner.predict_mc(mnist.validation.images[:eval_rows], None, FLAGS.mc_dropout_samples,
+                                                  use_ema=ema_eval), mnist.validation.labels[:eval_rows])
+        print(format_mc_dropout(mc, FLAGS.mc_dropout_samples, FLAGS.keep_prob))
+        metrics.log(event="mc_dropout", global_step=step, samples=FLAGS.mc_dropout_samples, keep_prob=FLAGS.keep_prob,
+                    **{k: (None if v != v else v) for k, v in mc.items()})
     skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
     if skipped > 0:
         print("Worker %d: --skip_nonfinite skipped %d of %d optimizer steps (aggregated gradient not finite)"

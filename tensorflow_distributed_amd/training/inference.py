@@ -76,6 +76,58 @@ def merge_records(records) -> dict:
             "correct": int(sum(r["correct"] for r in records)), "confusion": cm}
 
 
+MC_DROPOUT_KEY = 0x4D43D409  # csrc/mnist_mc.h kMcDropoutKey
+MC_MAX_SAMPLES = 4096        # kMcMaxSamples
+
+
+def mc_dropout_masks(rows: int, samples: int, row0: int, rank: int, seed: int, keep_prob: float) -> np.ndarray:
+    """The 0/1 masks ``[rows, samples, 1024]`` (float64) that ``mc_head_kernel`` draws (csrc/mnist_mc.h): hidden
+    unit ``u`` of sample ``s`` of global row ``r = row0 + i`` is word ``u % 4`` of the Philox4x32-10 call with
+    counter ``(s * 256 + u // 4, r lo, r hi, rank)`` and key ``(seed, MC_DROPOUT_KEY)``; kept iff ``u01 < keep_prob``
+    in fp32. The kernel's lane map only decides which lane makes which call."""
+    from ..models.mnist_cnn import HID, _philox4x32_10
+
+    r = (np.uint64(row0) + np.arange(rows, dtype=np.uint64))[:, None, None]
+    s = np.arange(samples, dtype=np.uint64)[None, :, None]
+    g = np.arange(HID // 4, dtype=np.uint64)[None, None, :]
+    shape = (rows, samples, HID // 4)
+    c0 = np.broadcast_to(s * np.uint64(256) + g, shape)
+    c1 = np.broadcast_to(r & np.uint64(0xFFFFFFFF), shape)
+    c2 = np.broadcast_to(r >> np.uint64(32), shape)
+    c3 = np.full(shape, rank & 0xFFFFFFFF, dtype=np.uint64)
+    out = _philox4x32_10((c0, c1, c2, c3), seed & 0xFFFFFFFF, MC_DROPOUT_KEY)
+    u = np.stack([(v >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0) for v in out], axis=-1)
+    return (u < np.float32(keep_prob)).reshape(rows, samples, HID).astype(np.float64)
+
+
+def mc_dropout_ref(h, W_out, b_out, masks, keep_prob: float, labels=None) -> dict:
+    """Monte-Carlo dropout statistics in fp64. ``h`` [rows, 1024] is the hidden layer before its relu, ``masks``
+    [rows, T, 1024] the kept units of every sample: ``logits[i, s] = (masks[i, s] * relu(h[i]) / keep_prob) @ W_out
+    + b_out``. Returns ``logits`` [rows, T, C], ``mean_prob`` (the mean softmax), ``classes`` (its first maximum),
+    ``entropy`` of the mean, ``expected_entropy`` (the mean of the samples' entropies), ``mutual_info`` (their
+    difference, BALD), ``var_prob`` (the samples' variance per class, divisor T) and, with labels, ``loss_rows =
+    -log mean_prob[label]`` and ``correct_rows``; ``0 log 0 = 0``."""
+    h, W, b, mk = (np.asarray(a, dtype=np.float64) for a in (h, W_out, b_out, masks))
+    a = mk * (np.maximum(h, 0.0) / float(keep_prob))[:, None, :]
+    z = a @ W + b
+    e = np.exp(z - z.max(-1, keepdims=True))
+    p = e / e.sum(-1, keepdims=True)
+
+    def ent(q):
+        return -(q * np.log(np.where(q > 0, q, 1.0))).sum(-1)
+
+    pbar = p.mean(1)
+    out = {"logits": z, "probs": p, "mean_prob": pbar, "classes": pbar.argmax(1).astype(np.int32), "entropy": ent(pbar),
+           "expected_entropy": ent(p).mean(1), "var_prob": ((p - pbar[:, None, :]) ** 2).mean(1)}
+    out["mutual_info"] = out["entropy"] - out["expected_entropy"]
+    if labels is not None:
+        y = _ids(labels, "labels")
+        with np.errstate(divide="ignore"):
+            out["loss_rows"] = -np.log(pbar[np.arange(len(y)), y])
+        out["correct_rows"] = (out["classes"] == y).astype(np.float64)
+    return out
+
+
 def _ratio(num: np.ndarray, den: np.ndarray) -> np.ndarray:
     out = np.full(num.shape, np.nan, dtype=np.float64)
     np.divide(num, den, out=out, where=den > 0)
