@@ -29,6 +29,7 @@
 #include "../mnist_input_grad.h"
 #include "../mnist_infer.h"
 #include "../mnist_mc.h"
+#include "../mnist_mx.h"
 #include "../mnist_layout.h"
 #include "../optim_launch.h"
 #include "../optim_q8.h"
@@ -743,6 +744,8 @@ class MnistEngine : public torch::CustomClassHolder {
                 "bf16 step's operands; set_adversarial(0, -1) first");
     TORCH_CHECK(dt == "bf16" || !dp_on_, "set_dtype('fp32') with set_dp_sgd on: the per-example norm kernel reads the bf16 "
                 "step's factors; set_dp_sgd(0, 0) first");
+    TORCH_CHECK(dt == "bf16" || mx_fmt_ < 0, "set_dtype('fp32') with set_infer_format('", infer_format(), "'): the block-scaled "
+                "fc1 quantises the bf16 engine's pooled activations; set_infer_format('bf16') first");
     const bool f = dt == "fp32";
     if (f && !f1_.defined()) {
       auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, device_);
@@ -759,6 +762,26 @@ class MnistEngine : public torch::CustomClassHolder {
     if (f) bf16_comm_ = false;
   }
   std::string dtype() const { return fp32_ ? "fp32" : "bf16"; }
+
+  // ---- inference format of fc1 (csrc/mnist_mx.h) ----
+  // "bf16" (default): predict / predict_mc / evaluate_dataset / capture_eval run fc1 as the step does. "mxfp8" /
+  // "mxfp4": they run it on the block-scaled matrix instruction, W1 packed from the fp32 master (or the EMA shadow)
+  // by one launch at the head of every call and of every evaluation graph, the pooled activations quantised to MXFP8
+  // in registers. evaluate() and every training path ignore the option.
+  void set_infer_format(const std::string& fmt) {
+    TORCH_CHECK(fmt == "bf16" || fmt == "mxfp8" || fmt == "mxfp4", "set_infer_format: 'bf16', 'mxfp8' or 'mxfp4', got '", fmt, "'");
+    TORCH_CHECK(fmt == "bf16" || !fp32_, "set_infer_format('", fmt, "') on the fp32 engine: the block-scaled fc1 quantises the "
+                "bf16 engine's pooled activations; set_dtype('bf16') first");
+    mx_fmt_ = fmt == "bf16" ? -1 : fmt == "mxfp4" ? (int)MX_FP4 : (int)MX_FP8;
+    if (mx_fmt_ < 0) return;
+    // Allocated once, at the larger (e4m3) size, and never replaced: an evaluation graph captured in one format holds
+    // these addresses and its own pack node, so it stays replayable after the format changes.
+    if (!mx_packed_.defined()) {
+      mx_packed_ = at::empty({(int64_t)mx_packed_bytes(MX_FP8)}, idx2_.options());
+      mx_slab_ = at::empty({kMxSplits, B_, HID}, fc1_slab_.options());
+    }
+  }
+  std::string infer_format() const { return mx_fmt_ < 0 ? "bf16" : mx_fmt_ == MX_FP4 ? "mxfp4" : "mxfp8"; }
 
   // ---- per-phase GPU timing ----
   // With timing on, train_step records HIP timing events at its phase boundaries -- also inside a
@@ -1555,6 +1578,7 @@ class MnistEngine : public torch::CustomClassHolder {
     auto correct = at::empty({labelled ? n : 0}, x.options());
     if (n == 0) return {logits, classes, loss, correct};
     refresh_ema_image(use_ema, stream());
+    mx_pack(use_ema, stream());
     for (int64_t o = 0; o < n; o += B_) {
       const int nb = (int)std::min<int64_t>(B_, n - o);
       InferHeadArgs h = infer_forward((const float*)x.data_ptr() + o * 784, nb, use_ema, stream());
@@ -1594,6 +1618,7 @@ class MnistEngine : public torch::CustomClassHolder {
     auto loss = at::empty({labelled ? n : 0}, x.options()), correct = at::empty({labelled ? n : 0}, x.options());
     if (n == 0) return {mean_prob, classes, entropy, mi, var_prob, loss, correct};
     refresh_ema_image(use_ema, stream());
+    mx_pack(use_ema, stream());
     for (int64_t o = 0; o < n; o += B_) {
       const int nb = (int)std::min<int64_t>(B_, n - o);
       const InferHeadArgs h = infer_forward((const float*)x.data_ptr() + o * 784, nb, use_ema, stream());
@@ -1625,8 +1650,8 @@ class MnistEngine : public torch::CustomClassHolder {
   // knows the chunk's rows and the split count itself; the view is stale after the next forward of any kind.
   at::Tensor infer_slabs() {
     TORCH_CHECK(infer_rows_ > 0, "infer_slabs: no inference forward has run");
-    const at::Tensor& s = fp32_ ? fslab_ : fc1_slab_;
-    const int64_t splits = fp32_ ? mnist_f32_fc1_splits() : fc1_splits_;
+    const at::Tensor& s = mx_fmt_ >= 0 ? mx_slab_ : fp32_ ? fslab_ : fc1_slab_;
+    const int64_t splits = mx_fmt_ >= 0 ? kMxSplits : fp32_ ? mnist_f32_fc1_splits() : fc1_splits_;
     return s.view({-1}).narrow(0, 0, splits * infer_rows_ * HID).view({splits, infer_rows_, HID});
   }
 
@@ -1660,6 +1685,7 @@ class MnistEngine : public torch::CustomClassHolder {
     auto rec = at::empty({(count + group - 1) / group, kEvalRecFields}, eval_x_.options().dtype(at::kDouble));
     if (count == 0) return rec;
     refresh_ema_image(use_ema, stream());
+    mx_pack(use_ema, stream());
     eval_launches(first, count, group, use_ema, (double*)rec.data_ptr(), stream());
     return rec;
   }
@@ -1675,9 +1701,11 @@ class MnistEngine : public torch::CustomClassHolder {
     drop_graph(name);
     auto rec = at::empty({(count + group - 1) / group, kEvalRecFields}, eval_x_.options().dtype(at::kDouble));
     if (use_ema && !fp32_ && !ema_bf_.defined()) ema_bf_ = at::empty_like(pbf_);
+    mx_pack(false, s);
     (void)infer_forward((const float*)eval_x_.data_ptr() + first * 784, (int)std::min(std::min(B_, group), count), false, s);
     StreamCapture cap(s);
     if (use_ema && !fp32_) cast_f32_bf16((const float*)ema_.data_ptr(), (uint16_t*)ema_bf_.data_ptr(), TOTAL, s);
+    mx_pack(use_ema, s);  // a node of the graph: a replay packs the weights of its own time
     eval_launches(first, count, group, use_ema, (double*)rec.data_ptr(), s);
     store_graph(name, cap);
     eval_recs_[name] = rec;
@@ -2250,6 +2278,11 @@ class MnistEngine : public torch::CustomClassHolder {
     if (ema_bf_stale_) cast_f32_bf16((const float*)ema_.data_ptr(), (uint16_t*)ema_bf_.data_ptr(), TOTAL, s);
     ema_bf_stale_ = false;
   }
+  // In an MX inference format: W1 of the master copy or the shadow -> the packed image infer_forward's fc1 reads
+  void mx_pack(bool use_ema, hipStream_t s) {
+    if (mx_fmt_ < 0) return;
+    mx_pack_fc1((const float*)(use_ema ? ema_ : params_).data_ptr() + OFF_WD1, (uint8_t*)mx_packed_.data_ptr(), mx_fmt_, s);
+  }
   // conv1, conv2 and fc1 over nb <= B fed rows at x, as evaluate() runs them; returns the inference
   // head's view of the slabs and the parameters (the caller sets the labels and the outputs)
   InferHeadArgs infer_forward(const float* x, int nb, bool use_ema, hipStream_t s) {
@@ -2272,6 +2305,12 @@ class MnistEngine : public torch::CustomClassHolder {
       mnist_f32_forward_nohead(f, s);
       h.fc1_slab = f.fc1_slab;
       h.splits = f.fc1_splits;
+    } else if (mx_fmt_ >= 0) {
+      mnist_forward_conv(a, s);
+      const MxFc1Args m{nb, a.p2, (const uint8_t*)mx_packed_.data_ptr(), (float*)mx_slab_.data_ptr()};
+      mx_fc1_fwd(m, mx_fmt_, s);
+      h.fc1_slab = m.slab;
+      h.splits = kMxSplits;
     } else {
       mnist_forward_nohead(a, s);
       h.fc1_slab = a.fc1_slab;
@@ -2411,6 +2450,8 @@ class MnistEngine : public torch::CustomClassHolder {
   uint32_t seed_, rank_;
   int fc1_splits_, wg2_splits_;
   int64_t infer_rows_ = 0;  // rows of the last inference forward (infer_slabs)
+  int mx_fmt_ = -1;         // set_infer_format: -1 = bf16, else an MxFormat
+  at::Tensor mx_packed_, mx_slab_;
   int64_t input_mode_ = 0;
   OptKind opt_ = OptKind::Adam;
   // RMSProp / Adagrad (set_rmsprop / set_adagrad): the rule's scalars and the centered rule's third slot
@@ -2633,6 +2674,8 @@ TORCH_LIBRARY_FRAGMENT(tfd, m) {
            {torch::arg("x"), torch::arg("y"), torch::arg("samples"), torch::arg("keep_prob"), torch::arg("seed"),
             torch::arg("use_ema") = false, torch::arg("row0") = 0})
       .def("infer_slabs", &MnistEngine::infer_slabs)
+      .def("set_infer_format", &MnistEngine::set_infer_format)
+      .def("infer_format", &MnistEngine::infer_format)
       .def("set_eval_dataset", &MnistEngine::set_eval_dataset)
       .def("eval_dataset_rows", &MnistEngine::eval_dataset_rows)
       .def("evaluate_dataset", &MnistEngine::evaluate_dataset, "",

@@ -7,7 +7,7 @@ dropout 0.75), same model (conv5x5x32-pool-conv5x5x64-pool-fc1024-dropout-fc10, 
 same loop (`while step * batch_size < training_iters`, a keep_prob=1 minibatch-loss forward every
 display_step), same 50 x 100 validation pass and the same stdout lines. On a GPU it runs the
 native HIP engine (one captured hipGraph per step); without one, fp32 PyTorch on the CPU.
-Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --dp_l2_norm_clip --dp_noise_multiplier --dp_delta --device_eval --confusion_matrix --mc_dropout_samples --logdir --cpu --data_dir --seed.
+Optional overrides: --training_iters --batch_size --learning_rate --optimizer --rmsprop_* --adagrad_init_accum --weight_decay --clip_norm --skip_nonfinite --ema_decay --grad_accum_steps --steps_per_call --augment_shift --augment_rotate --augment_scale --elastic_alpha --elastic_sigma --adv_eps --adv_rows --adv_eval_eps --dp_l2_norm_clip --dp_noise_multiplier --dp_delta --device_eval --confusion_matrix --mc_dropout_samples --infer_format --logdir --cpu --data_dir --seed.
 '''
 import argparse
 import os
@@ -20,7 +20,7 @@ import torch  # noqa: E402
 
 from tensorflow_distributed_amd.models import mnist_cnn as M  # noqa: E402
 from tensorflow_distributed_amd.models.mnist_runner import format_mc_dropout, make_runner, mc_dropout_summary  # noqa: E402
-from tensorflow_distributed_amd.training import checkpoint, inference  # noqa: E402
+from tensorflow_distributed_amd.training import checkpoint, inference, mx_quant  # noqa: E402
 from tensorflow_distributed_amd.training.augment import augment_config, augment_on  # noqa: E402
 from tensorflow_distributed_amd.training.step_calls import call_lengths, multiples  # noqa: E402
 from tensorflow_distributed_amd.training.optimizers import (Adam8bitOptimizer, AdagradOptimizer, AdamOptimizer,  # noqa: E402
@@ -119,6 +119,9 @@ def main(argv=None):
                     "this many dropout passes per row over the rows --device_eval evaluates (GPU: one launch per batch "
                     "behind one forward, csrc/mnist_mc.h); prints the accuracy of the mean prediction and the mean "
                     "predictive entropy and mutual information of the correct and the wrong rows; 0 = off")
+    ap.add_argument("--infer_format", default="bf16", choices=list(mx_quant.INFER_FORMATS), help="fc1 of --device_eval and "
+                    "--mc_dropout_samples: bf16 (the step's GEMM) or mxfp8 / mxfp4, W1 packed into the OCP MX block format "
+                    "and the product on the block-scaled matrix instruction (csrc/mnist_mx.h); training is not affected")
     ap.add_argument("--logdir", default="", help="write a TF-format checkpoint here after training (with --ema_decay "
                     "it carries <var>/ExponentialMovingAverage) and restore the latest one found here at start")
     a = ap.parse_args(argv)
@@ -137,6 +140,8 @@ def main(argv=None):
             ap.error("--steps_per_call > 1 with --no_graph: the steps of a call are one captured graph")
     if a.confusion_matrix and not a.device_eval:
         ap.error("--confusion_matrix is folded by --device_eval: give both")
+    if a.infer_format != "bf16" and a.dtype == "fp32" and not a.cpu and torch.cuda.is_available():
+        ap.error("--infer_format %s with --dtype fp32: the block-scaled fc1 quantises the bf16 engine's activations" % a.infer_format)
     if not 0 <= a.mc_dropout_samples <= inference.MC_MAX_SAMPLES:
         ap.error("--mc_dropout_samples must be in [0, %d] (0 = off)" % inference.MC_MAX_SAMPLES)
     augment = (a.augment_shift, a.augment_rotate, a.augment_scale, a.elastic_alpha, a.elastic_sigma)
@@ -190,6 +195,7 @@ def main(argv=None):
         opt = AdamOptimizer(a.learning_rate, **common)
     runner = make_runner(a.batch_size, opt, dev, keep_prob=dropout, seed=a.seed,
                          use_graph=not a.no_graph, dtype=a.dtype)
+    runner.set_infer_format(a.infer_format)
     runner.load_flat(M.flat_from_dict(M.init_params(a.seed)), {}, 0)  # init = initialize_all_variables()
     saver = checkpoint.Saver()
     latest = checkpoint.latest_checkpoint(a.logdir) if a.logdir else None

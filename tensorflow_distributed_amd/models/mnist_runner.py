@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from ..training.optimizers import (FlatApplier, base_optimizer, ema_decay_at, is_layerwise, is_schedule, lr_at,
                                    schedule_args)
-from ..training import inference
+from ..training import inference, mx_quant
 from . import mnist_cnn as M
 
 
@@ -519,6 +519,28 @@ class TorchMnistRunner(MnistRunnerBase):
 
     # ---- inference (training/inference.py holds the definitions) ----
     _PREDICT_CHUNK = 1000  # rows per forward: bounds the activations of a whole split
+    _infer_format = "bf16"
+
+    def set_infer_format(self, fmt: str) -> None:
+        """fc1 of ``predict``, ``predict_mc`` and ``evaluate_dataset``: ``"bf16"`` (the default: this runner's fp32
+        forward) or ``"mxfp8"`` / ``"mxfp4"``, the block-scaled product by its fp64 definition (``mx_quant.mx_fc1_ref``)
+        over the pooled activations rounded to bf16. ``evaluate`` and training ignore it."""
+        if fmt not in mx_quant.INFER_FORMATS:
+            raise ValueError(f"set_infer_format: one of {mx_quant.INFER_FORMATS}, got {fmt!r}")
+        self._infer_format = fmt
+
+    def infer_format(self) -> str:
+        return self._infer_format
+
+    def _fc1(self, x, p):
+        """fc1's pre-activation ``[rows, 1024]`` of the rows ``x`` in the inference format"""
+        a = x.reshape(-1, M.IMG, M.IMG, 1)
+        a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc1"], p["bc1"])), 2)
+        a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc2"], p["bc2"])), 2).reshape(-1, M.FEAT)
+        if self._infer_format == "bf16":
+            return a @ p["wd1"] + p["bd1"]
+        h = mx_quant.mx_fc1_ref(a.to(torch.bfloat16).float().cpu().numpy(), p["wd1"].cpu().numpy(), self._infer_format)
+        return torch.from_numpy(h).to(a.device, torch.float32) + p["bd1"]
 
     @torch.no_grad()
     def predict(self, x, use_ema: bool = False):
@@ -526,8 +548,12 @@ class TorchMnistRunner(MnistRunnerBase):
         first maximum of its logits. ``use_ema``: the moving averages in place of the parameters."""
         x = _as_rows(x).to(self.device)
         flat = self.ema_params() if use_ema else None
-        parts = [self._forward(x[o:o + self._PREDICT_CHUNK], 1.0, flat=flat)
-                 for o in range(0, x.shape[0], self._PREDICT_CHUNK)]
+        if self._infer_format == "bf16":
+            fwd = lambda rows: self._forward(rows, 1.0, flat=flat)  # noqa: E731
+        else:
+            p = M.dict_from_flat(self.flat if flat is None else flat)
+            fwd = lambda rows: torch.relu(self._fc1(rows, p)) @ p["out"] + p["out_b"]  # noqa: E731
+        parts = [fwd(x[o:o + self._PREDICT_CHUNK]) for o in range(0, x.shape[0], self._PREDICT_CHUNK)]
         logits = torch.cat(parts) if parts else torch.zeros(0, M.NCLS, device=self.device)
         # numpy's argmax returns the first maximum; torch's makes no promise about ties
         classes = torch.from_numpy(logits.cpu().numpy().argmax(1).astype(np.int32)) if len(parts) else \
@@ -547,10 +573,7 @@ class TorchMnistRunner(MnistRunnerBase):
         chunk = max(1, min(self._PREDICT_CHUNK, 4096 // int(samples)))
         parts = []
         for o in range(0, x.shape[0], chunk):
-            a = x[o:o + chunk].reshape(-1, M.IMG, M.IMG, 1)
-            a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc1"], p["bc1"])), 2)
-            a = M.maxpool_same_nhwc(torch.relu(M.conv2d_same_nhwc(a, p["wc2"], p["bc2"])), 2)
-            h = a.reshape(-1, M.FEAT) @ p["wd1"] + p["bd1"]
+            h = self._fc1(x[o:o + chunk], p)
             masks = inference.mc_dropout_masks(h.shape[0], samples, row0 + o, self._rank, seed, kp)
             parts.append(inference.mc_dropout_ref(h.cpu().numpy(), p["out"].cpu().numpy(), p["out_b"].cpu().numpy(), masks, kp,
                                                   None if ys is None else ys[o:o + chunk]))
@@ -1137,6 +1160,20 @@ class NativeMnistRunner(MnistRunnerBase):
         return float(r[0]), int(round(float(r[1])))
 
     # ---- device inference (csrc/mnist_infer.h) ----
+    def set_infer_format(self, fmt: str) -> None:
+        """fc1 of ``predict``, ``predict_mc`` and ``evaluate_dataset``: ``"bf16"`` (the default, the step's GEMM) or
+        ``"mxfp8"`` / ``"mxfp4"``: W1 packed into the OCP MX format from the fp32 master (or the EMA shadow) at the
+        head of every call, the pooled activations quantised to MXFP8 in registers, the product on the block-scaled
+        matrix instruction (csrc/mnist_mx.h). bf16 engine only. ``evaluate`` and training ignore it."""
+        if fmt not in mx_quant.INFER_FORMATS:
+            raise ValueError(f"set_infer_format: one of {mx_quant.INFER_FORMATS}, got {fmt!r}")
+        self.stream.synchronize()
+        self.eng.set_infer_format(fmt)
+        self._eval_graphs = set()  # an evaluation graph holds the format's launches: captured again at its next use
+
+    def infer_format(self) -> str:
+        return self.eng.infer_format()
+
     def predict(self, x, use_ema: bool = False):
         """``(logits [n,10] fp32, classes [n] int32)`` on the device: the forward up to fc1 and the
         inference head, rows in chunks of the engine's batch. ``use_ema`` as in ``evaluate``."""

@@ -2,7 +2,7 @@
 
     python -m tensorflow_distributed_amd.predict --logdir DIR [--split validation|test|train] [--use_ema]
         [--dtype bf16|fp32] [--out FILE.npz] [--confusion_matrix] [--data_dir DIR] [--rows N] [--batch_size N] [--cpu]
-        [--mc_dropout_samples T] [--keep_prob P]
+        [--mc_dropout_samples T] [--keep_prob P] [--infer_format bf16|mxfp8|mxfp4]
 
 Restores the latest checkpoint under ``--logdir`` (mnist_single.py --logdir, dist_main's Supervisor),
 runs the forward over one split of the data set -- on a GPU through the native engine's inference head
@@ -22,7 +22,7 @@ import torch
 
 from .models import mnist_cnn as M
 from .models.mnist_runner import EMA_SUFFIX, format_mc_dropout, make_runner, mc_dropout_summary
-from .training import checkpoint, inference
+from .training import checkpoint, inference, mx_quant
 from .training.optimizers import AdamOptimizer
 from .utils import input_data
 
@@ -46,7 +46,11 @@ def main(argv=None) -> int:
                     "mutual information of the correct and the wrong rows, and adds mean_prob, entropy, mutual_info and "
                     "var_prob to --out; 0 = off")
     ap.add_argument("--keep_prob", type=float, default=0.75, help="--mc_dropout_samples: the dropout keep probability")
+    ap.add_argument("--infer_format", default="bf16", choices=list(mx_quant.INFER_FORMATS), help="fc1's format: bf16, or "
+                    "mxfp8 / mxfp4 = W1 in the OCP MX block format on the block-scaled matrix instruction (csrc/mnist_mx.h)")
     a = ap.parse_args(argv)
+    if a.infer_format != "bf16" and a.dtype == "fp32" and not a.cpu and torch.cuda.is_available():
+        ap.error("--infer_format %s with --dtype fp32: the block-scaled fc1 quantises the bf16 engine's activations" % a.infer_format)
     if a.batch_size < 1:
         ap.error("--batch_size must be >= 1")
     if not 0 <= a.mc_dropout_samples <= inference.MC_MAX_SAMPLES or not 0 < a.keep_prob <= 1:
@@ -63,6 +67,7 @@ def main(argv=None) -> int:
     opt = AdamOptimizer(0.01, **(dict(ema_decay=0.5, ema_num_updates=False) if a.use_ema else {}))
     runner = make_runner(a.batch_size, opt, dev, keep_prob=1.0, seed=a.seed, use_graph=False, dtype=a.dtype)
     runner.load_state_dict_tf(tensors)
+    runner.set_infer_format(a.infer_format)
     print("Restored %s (global step %d)%s" % (latest, runner.global_step(), "; predicting from the moving averages"
                                               if a.use_ema else ""))
     split = getattr(input_data.read_data_sets(a.data_dir, one_hot=True, seed=a.seed), a.split)

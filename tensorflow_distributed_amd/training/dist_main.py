@@ -152,6 +152,10 @@ def define_flags(task_index_default: int = 0, job_name_default: str = "ps") -> N
                      "csrc/mnist_mc.h); prints MC-dropout Testing Accuracy with the mean predictive entropy and mutual "
                      "information of the correct and the wrong rows, and logs an mc_dropout record. --model mnist_cnn, "
                      "synchronous all-reduce training; 0 = off")
+    f.DEFINE_string("infer_format", "bf16", "fc1 of --device_eval and --mc_dropout_samples: bf16 (the step's GEMM), or "
+                    "mxfp8 / mxfp4 = W1 packed into the OCP MX block format and the product on the block-scaled matrix "
+                    "instruction (csrc/mnist_mx.h); the evaluation record carries infer_format. --model mnist_cnn, "
+                    "synchronous all-reduce training; training itself is not affected")
     f.DEFINE_string("metrics_file", "", "Chief: JSONL metrics per step")
     f.DEFINE_string("trace_file", "", "Chrome-trace JSON of host step phases")
     f.DEFINE_integer("check_consistency_every", 0, "Every N steps all-reduce a param checksum and "
@@ -554,6 +558,27 @@ def check_mc_dropout_flags(num_workers: int) -> None:
                          "python -m tensorflow_distributed_amd.predict --mc_dropout_samples")
     if FLAGS.eval_batches < 1 or FLAGS.eval_batch_size < 1:
         raise ValueError("--mc_dropout_samples: --eval_batches and --eval_batch_size must be >= 1")
+
+
+def check_infer_format_flags(num_workers: int) -> None:
+    """--infer_format sets fc1's format on the worker's engine; it refuses what --device_eval refuses."""
+    from .mx_quant import INFER_FORMATS
+
+    if FLAGS.infer_format not in INFER_FORMATS:
+        raise ValueError("--infer_format must be one of %s" % ", ".join(INFER_FORMATS))
+    if FLAGS.infer_format == "bf16":
+        return
+    if FLAGS.model != "mnist_cnn":
+        raise ValueError("--infer_format %s with --model %s: the block-scaled kernel is the MNIST CNN's fc1"
+                         % (FLAGS.infer_format, FLAGS.model))
+    r2a = FLAGS.replicas_to_aggregate
+    if not FLAGS.sync_replicas or (r2a is not None and r2a < num_workers and bool(FLAGS.ps_hosts)):
+        raise ValueError("--infer_format in the parameter-server role (--sync_replicas=False, or backup workers with "
+                         "--ps_hosts): the variables live on the ps tasks; evaluate a checkpoint of such a run with "
+                         "python -m tensorflow_distributed_amd.predict --infer_format")
+    if FLAGS.num_gpus > 0 and FLAGS.dtype == "fp32":
+        raise ValueError("--infer_format %s with --dtype fp32: the block-scaled fc1 quantises the bf16 engine's "
+                         "activations" % FLAGS.infer_format)
 
 
 def check_ema_flags(num_workers: int) -> None:
@@ -1004,6 +1029,7 @@ def main(argv=None) -> int:
     check_dp_sgd_flags(len(FLAGS.worker_hosts.split(",")))
     check_device_eval_flags(len(FLAGS.worker_hosts.split(",")))
     check_mc_dropout_flags(len(FLAGS.worker_hosts.split(",")))
+    check_infer_format_flags(len(FLAGS.worker_hosts.split(",")))
 
     print("job name = %s" % FLAGS.job_name)
     print("task index = %d" % FLAGS.task_index)
@@ -1153,6 +1179,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         return len(val_x), runner.evaluate(val_x, val_y, use_ema=ema_eval)[1]
 
     eval_rows = min(FLAGS.eval_batches * FLAGS.eval_batch_size, mnist.validation.num_examples)
+    if FLAGS.infer_format != "bf16":
+        runner.set_infer_format(FLAGS.infer_format)
     if FLAGS.device_eval:
         runner.set_eval_dataset(mnist.validation.images, mnist.validation.labels)  # uploaded once
 
@@ -1318,7 +1346,8 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
         mean_accuracy = _validate(iter(batches).__next__, len(batches))
         whole = inference.merge_records(recs)
         evaluation = dict(event="evaluation", global_step=step, rows=whole["rows"], correct=whole["correct"],
-                          loss=whole["loss_sum"] / max(whole["rows"], 1), mean_accuracy=mean_accuracy)
+                          loss=whole["loss_sum"] / max(whole["rows"], 1), mean_accuracy=mean_accuracy,
+                          infer_format=FLAGS.infer_format)
         if adv_eval["on"]:
             adversarial_rows(mnist.validation.images[:eval_rows], mnist.validation.labels[:eval_rows])
             evaluation.update(adv_accuracy=adv_eval["correct"] / float(max(adv_eval["rows"], 1)), adv_eps=FLAGS.adv_eval_eps)
@@ -1342,6 +1371,7 @@ def _mnist_worker(server, cluster, roles: Roles, layout, opt, mnist) -> int:
                                                   use_ema=ema_eval), mnist.validation.labels[:eval_rows])
         print(format_mc_dropout(mc, FLAGS.mc_dropout_samples, FLAGS.keep_prob))
         metrics.log(event="mc_dropout", global_step=step, samples=FLAGS.mc_dropout_samples, keep_prob=FLAGS.keep_prob,
+                    infer_format=FLAGS.infer_format,
                     **{k: (None if v != v else v) for k, v in mc.items()})
     skipped = runner.skipped_steps() if opt.skip_nonfinite else 0
     if skipped > 0:
